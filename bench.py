@@ -6,12 +6,16 @@ N=512, nu=2 (BASELINE.json metric / configs).  Each rank owns ONE independent pr
 diffusion-coefficient sweep kappa_g = 0.01 * 10^(g/7): weak scaling, no collective
 in the data path; RCCL only gathers the per-rank read-outs at the end.
 
-Prints ONE JSON line (rank 0).  The timed region is K steps in one device call, bracketed by a barrier and a
-device sync on both sides, max over ranks; it is repeated `--repeats` (5) times and `value` / `ms_per_step`
-are the MEDIAN repeat (`ms_per_step_all` lists them).  `roofline` prices the whole step against the fp64
-MFMA peak with the ALGORITHMIC flop count F_alg of SURVEY.md section 8d (never the padded/dense count);
-`cpu_baseline` times the oracle (reference algorithm as written, NumPy/LAPACK) on this box's cores.
-At N=1 the line also carries (each driver-timed inside this run):
+Prints ONE JSON line (rank 0).  The timed region is K steps in device calls of at most SEGMENT steps, each bracketed
+by a barrier and a device sync on both sides, max over ranks; a plain run times it once, so exactly K steps are timed
+and `value` / `ms_per_step` are that region's.  `roofline` prices the whole step against the fp64 MFMA peak with the
+ALGORITHMIC flop count F_alg of SURVEY.md section 8d (never the padded/dense count).
+`--dump-outputs DIR` writes the read-outs of the last timed call to DIR/<name>.npy (see dump_outputs).
+
+`--full` adds what the headline figure does not need: the timed region is repeated `--repeats` (5) times and `value` /
+`ms_per_step` are the MEDIAN repeat (`ms_per_step_all` lists them); `cpu_baseline` times the oracle (reference
+algorithm as written, NumPy/LAPACK) on this box's cores.  At N=1 the --full line also carries (each driver-timed
+inside this run):
   batch8_on_1gpu   the 8-problem kappa sweep on this ONE GPU, problems one after the other and all in flight
                    -- the 1-GPU baseline north_star's ">= 6x at 8 GPUs on an 8-problem batch" refers to
   secondary        ms/step at N=256, N=1024 (fp64) and on the 64x64 2-d mesh (fp64 and fp32 covariance): BASELINE configs 2, 3, 5;
@@ -275,15 +279,51 @@ def library_baseline_ms():
         return None
 
 
+DUMP_BYTES = 64 * 10 ** 6   # cap on what --dump-outputs writes
+# Longest device call.  In fp64 the covariance form of the bench problems stops being positive definite after ~1650
+# steps at kappa = 0.05 (~1300 at kappa = 0.1, the top of the sweep), so longer runs are cut into calls that each
+# restart from the same state (see main).
+SEGMENT = 500
+
+
+def segments(k):
+    """k steps as near-equal device calls of at most SEGMENT steps."""
+    n = -(-k // SEGMENT)
+    return [k // n + (i < k % n) for i in range(n)]
+
+
+def dump_outputs(outdir, results):
+    """The read-outs of the last timed call as its caller receives them (`Filter.steps_end`), stacked over this rank's
+    problems: means / stds (B, K, d) and the per-step scalars of `StepOut` (B, K), all float64.  Above DUMP_BYTES the K
+    steps are cut to a fixed seeded sample (in step order; `t_new` says which steps were kept)."""
+    arrays = {"means": np.stack([r[0] for r in results]), "stds": np.stack([r[1] for r in results])}
+    for name in ("t_new", "diffusion_squared_local", "sigma2_whitened", "error_sigma2"):
+        arrays[name] = np.array([[getattr(o, name) for o in infos] for _, _, infos in results])
+    k = arrays["means"].shape[1]
+    per_step = sum(a[:, 0].nbytes for a in arrays.values())
+    if per_step * k > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(k, DUMP_BYTES // per_step, replace=False))
+        arrays = {name: a[:, rows] for name, a in arrays.items()}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K-step region; the median is reported")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 5 timed repeats (median reported), the CPU "
+                         "baseline and, at N=1, batch8_on_1gpu, the secondary points and the library baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the read-outs of the last timed call (rank 0's problems) to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the K-step region; the median is reported (default 1, 5 with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip batch8_on_1gpu, the secondary points and the library baseline (N=1 only has them)")
+                    help="--full without batch8_on_1gpu, the secondary points and the library baseline (N=1 only has them)")
     ap.add_argument("--problems-per-gpu", type=int, default=1,
                     help="independent problems run concurrently on each GPU (one context/stream and host thread each); "
                          "the headline metric uses 1")
@@ -291,6 +331,7 @@ def main():
                     help="secondary measurement points (BASELINE configs 256 / 1024); the headline metric is 512")
     args = ap.parse_args()
     globals()["MESH_N"] = args.mesh_n
+    repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
 
     limit_blas_threads()
     rank = int(os.environ.get("RANK", "0"))
@@ -330,7 +371,7 @@ def main():
         gidx = rank * B + b
         kappa = 0.05 if world * B == 1 else batch.diffusion_sweep(gidx, max(world * B, 8))
         kappas.append(kappa)
-        probs.append(_bound_problem(kappa, args.warmup + args.steps * max(1, args.repeats), device))
+        probs.append(_bound_problem(kappa, args.warmup + args.steps * repeats, device))
 
     def sync_all():
         for ctx, _, _ in probs:
@@ -340,32 +381,42 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def run_all(k, outputs):
+    def run_all(states, k, outputs):
         # enqueue every problem's k steps (asynchronous), then collect: the streams run concurrently on the device
-        for _, flt, dev in probs:
-            flt.steps_begin(dev, k, DT)
-        return [flt.steps_end(dev, want_means=outputs, want_stds=outputs) for _, flt, dev in probs]
+        for (_, flt, _), st in zip(probs, states):
+            flt.steps_begin(st, k, DT)
+        return [flt.steps_end(st, want_means=outputs, want_stds=outputs) for (_, flt, _), st in zip(probs, states)]
 
-    if args.warmup > 0:
-        run_all(args.warmup, False)
+    # The host-side setup above (LAPACK on many threads) can exhaust the container's CPU quota; the kernel then
+    # throttles the whole process for the rest of the 100 ms period, which shows up as a 20-90 ms hole in a 10-20 ms
+    # timed region (seen in 1 of 6 runs at N=256).  Let the quota refill before the device work.  The pause comes
+    # before the warm-up, not before the timed region: a timed region that follows an idle GPU ran 1-4 % slower.
+    time.sleep(float(os.environ.get("PNMOL_BENCH_SETTLE", "0.3")))
+    # Device calls of at most SEGMENT steps: the first warm-up call advances the problems; every later call (warm-up or
+    # timed) runs on an exact copy of where that call ended, so no problem is ever stepped past 2 * SEGMENT steps.
+    starts = [dev for _, _, dev in probs]
+    for i, k in enumerate(segments(args.warmup)):
+        run_all(starts if i == 0 else [s.clone() for s in starts], k, False)
     walls, devs, results = [], [], None
-    for rep in range(max(1, args.repeats)):
-        for _, flt, dev in probs:
-            flt.prepare_steps(dev, args.steps, DT)   # one-off host work (buffers, hipGraph instantiation)
-        # The host-side setup above (LAPACK on many threads) can exhaust the container's CPU quota; the kernel then
-        # throttles the whole process for the rest of the 100 ms period, which shows up as a 20-90 ms hole in a 10-20 ms
-        # timed region (seen in 1 of 6 runs at N=256).  Let the quota refill before timing; the GPU work is unaffected.
-        if rep == 0:
-            time.sleep(float(os.environ.get("PNMOL_BENCH_SETTLE", "0.3")))
-        sync_all()
-        t0 = time.perf_counter()
-        results = run_all(args.steps, True)                   # K steps per problem, one host sync at the end
-        sync_all()
-        wall = time.perf_counter() - t0
+    for rep in range(repeats):
+        wall = dev_ms = 0.0
+        for k in segments(args.steps):
+            states = None                                 # (frees the previous call's copies first)
+            states = [s.clone() for s in starts]
+            for (_, flt, _), st in zip(probs, states):
+                flt.prepare_steps(st, k, DT)              # host work and a rehearsal (buffers, hipGraph instantiation)
+            sync_all()
+            t0 = time.perf_counter()
+            results = run_all(states, k, True)            # k steps per problem, one host sync at the end
+            sync_all()
+            wall += time.perf_counter() - t0
+            dev_ms += max(p[1].last_steps_ms() for p in probs)  # HIP events on each problem's stream
         if dist is not None:
             wall = batch.max_over_ranks(wall, dist, device=coll_dev, force=force_dist)
         walls.append(wall)
-        devs.append(max(p[1].last_steps_ms() for p in probs))  # HIP events on each problem's stream
+        devs.append(dev_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results)
     order = np.argsort(walls)
     med = int(order[len(order) // 2])
     wall, dev_ms = walls[med], devs[med]
@@ -421,10 +472,10 @@ def main():
                                  "B_alg = %.3g" % (flops, 3 * D * D * 8)},
         }
         if world == 1:
-            line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline()
-            if not args.no_extras and B == 1 and MESH_N == 512:
-                del probs[:]                                  # release the headline problem's device memory first
-                line["batch8_on_1gpu"] = batch8_on_one_gpu(device, args.steps)
+            line["cpu_baseline"] = cpu_baseline() if args.full and not args.no_cpu_baseline else None
+            if args.full and not args.no_extras and B == 1 and MESH_N == 512:
+                del probs[:], starts[:], states[:]            # release the headline problem's device memory first
+                line["batch8_on_1gpu"] = batch8_on_one_gpu(device, min(args.steps, SEGMENT // 2))  # steps each problem 2 + 2K times
                 line["secondary"] = secondary_points(device)
                 line["library_baseline_ms_per_step"] = library_baseline_ms()
         else:

@@ -5,6 +5,8 @@ import pathlib
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 
 
@@ -33,3 +35,61 @@ def test_f_alg_matches_survey_table():
     assert abs(bench.f_alg(1536, 514, 3) / 1e9 - 1.70) < 0.01
     assert abs(bench.f_alg(768, 258, 3) / 1e9 - 0.218) < 0.002
     assert abs(bench.f_alg(3072, 1026, 3) / 1e9 - 13.4) < 0.1
+
+
+def test_segments_cover_the_steps_in_bounded_calls():
+    """bench.py times K steps in device calls of at most SEGMENT steps (the covariance form of the bench problem stops
+    being positive definite after ~1300-1600 steps); the calls add up to exactly K."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    assert bench.segments(0) == []
+    assert bench.segments(100) == [100]
+    for k in (1, bench.SEGMENT, bench.SEGMENT + 1, 3 * bench.SEGMENT - 1, 20000, 123457):
+        s = bench.segments(k)
+        assert sum(s) == k and max(s) <= bench.SEGMENT and max(s) - min(s) <= 1
+
+
+def _fake_readouts(problems, k, d):
+    from pnmol._hip import StepOut
+
+    rng, out = np.random.default_rng(1), []
+    for _ in range(problems):
+        infos = (StepOut * k)()
+        for i in range(k):
+            infos[i].t_new, infos[i].diffusion_squared_local, infos[i].info = (i + 1) * 2.0 ** -7, rng.random(), -1
+        out.append((rng.standard_normal((k, d)), rng.random((k, d)), infos))
+    return out
+
+
+def test_dump_outputs_writes_float64_readouts(tmp_path):
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    res = _fake_readouts(2, 30, 16)
+    bench.dump_outputs(tmp_path, res)
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == ["diffusion_squared_local.npy", "error_sigma2.npy", "means.npy", "sigma2_whitened.npy", "stds.npy",
+                     "t_new.npy"]
+    means, t = np.load(tmp_path / "means.npy"), np.load(tmp_path / "t_new.npy")
+    assert means.dtype == np.float64 and means.shape == (2, 30, 16) and t.shape == (2, 30)
+    np.testing.assert_array_equal(means[1], res[1][0])
+    np.testing.assert_array_equal(np.load(tmp_path / "stds.npy")[0], res[0][1])
+
+
+def test_dump_outputs_samples_large_readouts_the_same_way_every_time(tmp_path, monkeypatch):
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    res = _fake_readouts(1, 400, 64)                       # 400 steps * (2 * 64 + 4) * 8 B = 422 kB > the cap
+    bench.dump_outputs(tmp_path / "a", res)
+    bench.dump_outputs(tmp_path / "b", res)
+    total = sum(p.stat().st_size - 128 for p in (tmp_path / "a").iterdir())   # (npy header: 128 B)
+    assert total <= 200_000
+    for p in (tmp_path / "a").iterdir():
+        np.testing.assert_array_equal(np.load(p), np.load(tmp_path / "b" / p.name))
+    means, t = np.load(tmp_path / "a" / "means.npy"), np.load(tmp_path / "a" / "t_new.npy")
+    rows = np.rint(t[0] / 2.0 ** -7).astype(int) - 1       # the steps kept, in order
+    assert len(rows) > 100 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(means[0], res[0][0][rows])
