@@ -123,7 +123,9 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dds, const double
 /* The same for a POINTWISE nonlinearity, whose Jacobian is diagonal (`df_diagonal` of the reference's problem classes,
  * pde/problems.py; spruce budworm: pde/examples.py:292-341): M = L + diag(jdiag) with the L given at creation.  d + d numbers
  * cross the bus instead of a dense (d, d_state) matrix, the stencil rows are patched on the device (no host scan of M, no
- * stream synchronisation, captured graphs stay valid).  -1 if a row of L has no diagonal entry. */
+ * stream synchronisation, captured graphs stay valid).  Valid after any `pnmol_filter_set_operator`, in any order: the first
+ * call after a dense upload restores L's stencil rows first (whatever the dense operator's width or row pattern; captured
+ * graphs are dropped only if the width changes).  -1 if a row of L has no diagonal entry. */
 int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, const double* shift_d);
 
 /* states ----------------------------------------------------------------------------- */

@@ -3503,6 +3503,7 @@ struct pnmol_filter {
     double* ell_val_base = nullptr;
     int* ell_diag_slot = nullptr;
     int base_w = 0, base_has_diag = 0;
+    int ell_is_base = 1;      // ell_col / ell_val hold the base image (diagonal slots aside): no dense upload since the last restore
     double* h_op = nullptr;
     double* h_op_dev = nullptr;
     hipEvent_t ev_op = nullptr;
@@ -4407,6 +4408,7 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
         f->ell_cap = w;
     }
     f->ellw = w;
+    f->ell_is_base = 0;
     HIPCHK(ctx, hipMemcpy(f->ell_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(f->ell_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
     std::vector<double> sh((size_t)f->mp, 0.0);
@@ -4429,11 +4431,15 @@ int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, c
     const int d = f->d, mp = f->mp;
     std::memcpy(f->h_op, jdiag_d, sizeof(double) * d);
     for (int i = 0; i < mp; ++i) f->h_op[d + i] = (shift_d && i < d) ? shift_d[i] : 0.0;
-    if (f->ellw != f->base_w) {  // a dense pnmol_filter_set_operator came in between: back to the base image
-        drop_graphs(f);
+    if (!f->ell_is_base) {  // a dense pnmol_filter_set_operator came in between: back to the base image, whatever its width
+        // (a dense M of L's width can hold other off-diagonal values, or -- build_ell drops exact zeros -- another row pattern
+        // that moves the diagonal out of ell_diag_slot).  The copies go into the same buffers: captured graphs stay valid
+        // unless the width changes.
+        if (f->ellw != f->base_w) drop_graphs(f);
         HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->ell_col_base, sizeof(int) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
         HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->ell_val_base, sizeof(double) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
         f->ellw = f->base_w;
+        f->ell_is_base = 1;
     }
     k_operator_diagonal<<<(unsigned)((mp + 255) / 256), 256, 0, st>>>(f->ell_val, f->ell_val_base, f->ell_diag_slot, f->h_op_dev,
                                                                        f->shift, d, mp);

@@ -18,6 +18,7 @@
 // end: the canonical representative of the reference's factor (its signs are LAPACK's, arbitrary).
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -149,18 +150,51 @@ __device__ __forceinline__ float rcp_full(float x) {
     const float r = __builtin_amdgcn_rcpf(x);
     return r * (2.0f - x * r);
 }
-// dlarfg: a column whose entries below the diagonal have a sum of squares at or below this counts as already eliminated (tau = 0).
-// fp64: exactly zero, as LAPACK.  fp32: squares below ~1e-38 are denormal -- entries of 1e-19.5 .. 1e-22.5, which the noise-free
-// Dirichlet rows produce from N ~ 1000 on (smaller ones square to zero and took the tau = 0 path all along) -- and v_rsq_f32 of a
-// denormal is inf: NaNs from the first step at N = 1024.  Everything below 3e-18 in absolute value is dropped instead; the matrix's
-// own entries are 1e-10 .. 1e3 at 6e-8 relative.
-template <typename T> __device__ __forceinline__ T dlarfg_negligible();
-template <> __device__ __forceinline__ double dlarfg_negligible<double>() { return 0.0; }
-template <> __device__ __forceinline__ float dlarfg_negligible<float>() { return 1e-35f; }
+// dlarfg's guard.  fp64: tau = 0 only for an exactly zero column below the diagonal, as LAPACK.  fp32: what is unsafe is a
+// norm^2 = alpha^2 + sJ below FLT_MIN (v_rsq_f32 of a denormal is inf: NaNs from the first step at N = 1024, where the noise-free
+// Dirichlet rows leave entries of 1e-19.5 .. 1e-22.5), not a small column, and the stacked matrices are graded (entries 1e-10 ..
+// 1e3 at unit scale, times the scale of the square-root factors).  So the common path runs while sJ >= 2^-100 (its squares are
+// then exact to 2^-40 relative whatever their own size, and norm^2 is normal); below that -- a rare branch, uniform over the
+// column's lanes -- sJ is formed again from the entries times 2^64 (exact: a power of two, as LAPACK's xLARFG rescales by
+// safmin), alpha likewise, beta is scaled back, and the column's entries stay times 2^64 as its (unscaled) reflector: the
+// trailing update multiplies them into the other columns, and unscaled they would make denormal products there (which
+// wrecked the latent-force model at N = 96 in a first version that kept them unscaled).  tau = 0 there only when the scaled
+// sJ is <= eps^2 alpha^2 (x negligible against alpha, exactly zero included) or the scaled norm^2 is still below FLT_MIN (the
+// column itself is at the fp32 denormal level).  sJ == 0 is tau = 0 without that branch (structural zeros below the diagonal are
+// common: the triangular blocks of the stacked matrices); a column whose entries are all below 2^-75 ~ 2.6e-23, whose squares
+// underflow to zero, is the one case still counted as eliminated by size alone -- 5 orders of magnitude below the absolute cut
+// at 3e-18 this guard replaces.
 __device__ __forceinline__ double abs_t(double x) { return fabs(x); }
 __device__ __forceinline__ float abs_t(float x) { return fabsf(x); }
 __device__ __forceinline__ double copysign_t(double x, double y) { return copysign(x, y); }
 __device__ __forceinline__ float copysign_t(float x, float y) { return copysignf(x, y); }
+constexpr float DLARFG_SMALL = 0x1p-100f, DLARFG_UP = 0x1p64f, DLARFG_DOWN = 0x1p-64f, DLARFG_EPS2 = 0x1p-48f;
+// dlarfg: H = I - tau v v^T, v = [1; x / (alpha - beta)], beta = -sign(alpha) |(alpha, x)|; with nrm = |(alpha, x)|:
+// tau = (beta - alpha) / beta = 1 + |alpha| / nrm, 1 / (alpha - beta) = sign(alpha) / (|alpha| + nrm) -- one rsqrt and one
+// reciprocal on the step's critical path instead of a sqrt and two divisions
+template <typename T>
+__device__ __forceinline__ void dlarfg_scalars(T alpha, T sJ, T& beta, T& tau, T& scale) {
+    const T n2 = alpha * alpha + sJ, aa = abs_t(alpha);
+    const T rn = rsq_full(n2);
+    const T nrm = n2 * rn, den = aa + nrm;
+    const T rd = rcp_full(den);
+    beta = -copysign_t(nrm, alpha);
+    tau = T(1) + aa * rn;
+    scale = copysign_t(rd, alpha);
+}
+// fp32, sJ < DLARFG_SMALL: the same from sJs = sJ 2^128 (formed from the entries times 2^64) and alpha 2^64.  `scale` is
+// the one of the column x 2^64: the caller keeps the column's entries below the diagonal (the unscaled reflector, which
+// the trailing update multiplies into the other columns) times 2^64 from here on, so that those products stay normal.
+__device__ __forceinline__ void dlarfg_scalars_small(float alpha, float sJs, float& beta, float& tau, float& scale) {
+    const float as = alpha * DLARFG_UP, a2 = as * as, n2 = a2 + sJs;   // (a2 = inf for |alpha| >= 1: negligible x)
+    if (sJs > DLARFG_EPS2 * a2 && n2 >= FLT_MIN) {
+        const float aa = fabsf(as), rn = rsq_full(n2);
+        const float nrm = n2 * rn, rd = rcp_full(aa + nrm);
+        beta = -copysignf(nrm * DLARFG_DOWN, alpha);
+        tau = 1.0f + aa * rn;
+        scale = copysignf(rd, alpha);
+    }
+}
 
 // Householder QR of one chunk's panel (CR x 32).  Thread (k, g) = (t >> 4, t & 15) keeps rows g, g+16, ... of column k in
 // registers, so the 16 row groups of a column sit in ONE wave: the inner products of column J with the wave's own four
@@ -278,14 +312,31 @@ __device__ __forceinline__ void qr_factor_body(unsigned char* lds_raw, T* __rest
         sJ = group_sum<NG>(sJ);
         const T alpha = a[JN / NG];   // (the lane g == JN % NG holds row JN)
         T beta = alpha, tau = T(0), scale = T(0);
-        if (!(sJ <= dlarfg_negligible<T>())) {
-            const T n2 = alpha * alpha + sJ, aa = abs_t(alpha);
-            const T rn = rsq_full(n2);
-            const T nrm = n2 * rn, den = aa + nrm;
-            const T rd = rcp_full(den);
-            beta = -copysign_t(nrm, alpha);
-            tau = T(1) + aa * rn;
-            scale = copysign_t(rd, alpha);
+        if constexpr (sizeof(T) == 8) {
+            if (!(sJ <= 0.0)) dlarfg_scalars(alpha, sJ, beta, tau, scale);
+        } else {
+            if (!(sJ < DLARFG_SMALL)) dlarfg_scalars(alpha, sJ, beta, tau, scale);
+            const bool rare = sJ < DLARFG_SMALL && sJ != 0.0f;   // (the same in all lanes of the column)
+            // a wave-uniform branch (the whole wave runs this lambda): the common path pays two compares and a scalar branch,
+            // no exec-mask bookkeeping around a divergent block in the issue-bound column loop
+            if (__builtin_amdgcn_ballot_w64(rare)) {
+                T ps[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int r = 0; r < RPT; ++r)
+                    if (NG * r + NG - 1 > JN) {
+                        const T v = (NG * r > JN || g + NG * r > JN) ? a[r] * DLARFG_UP : T(0);
+                        ps[r & 3] += v * v;
+                    }
+                const T sJs = group_sum<NG>((ps[0] + ps[1]) + (ps[2] + ps[3]));
+                if (rare) {
+                    dlarfg_scalars_small(alpha, sJs, beta, tau, scale);
+                    if (k == JN) {   // the reflector times 2^64 (dlarfg_scalars_small), in the registers and in L.col
+#pragma unroll
+                        for (int r = 0; r < RPT; ++r) a[r] *= DLARFG_UP;
+                        col_store(JN & 1);
+                    }
+                }
+            }
         }
         if (k == JN && g == JN % NG) L.tau[JN] = tau, L.scale[JN] = scale, L.beta[JN] = beta;
     };
@@ -342,21 +393,30 @@ __device__ __forceinline__ void qr_factor_body(unsigned char* lds_raw, T* __rest
             sk = dpp_add<0x4E>(sk), sJ = dpp_add<0x4E>(sJ);
             sk = dpp_add<0x141>(sk), sJ = dpp_add<0x141>(sJ);
         }
-        // dlarfg: H = I - tau v v^T, v = [1; x / (alpha - beta)], beta = -sign(alpha) |(alpha, x)|; with
-        // nrm = |(alpha, x)|: tau = (beta - alpha) / beta = 1 + |alpha| / nrm, 1 / (alpha - beta) = sign(alpha) / (|alpha| + nrm)
-        // -- one rsqrt and one reciprocal on the step's critical path instead of a sqrt and two divisions
+        // dlarfg (dlarfg_scalars, with the guard above)
         const T alpha = L.rowb[cur][J], aJk = L.rowb[cur][k];
         T beta = alpha, tau = T(0), scale = T(0);
         if constexpr (OWN) {
             tau = L.tau[J], scale = L.scale[J], beta = L.beta[J];
-        } else if (!(sJ <= dlarfg_negligible<T>())) {
-            const T n2 = alpha * alpha + sJ, aa = abs_t(alpha);
-            const T rn = rsq_full(n2);
-            const T nrm = n2 * rn, den = aa + nrm;
-            const T rd = rcp_full(den);
-            beta = -copysign_t(nrm, alpha);
-            tau = T(1) + aa * rn;
-            scale = copysign_t(rd, alpha);
+        } else if constexpr (sizeof(T) == 8) {
+            if (!(sJ <= 0.0)) dlarfg_scalars(alpha, sJ, beta, tau, scale);
+        } else if (!(sJ < DLARFG_SMALL)) {
+            dlarfg_scalars(alpha, sJ, beta, tau, scale);
+        } else if (sJ != 0.0f) {   // (rare; sJ, alpha: the same in the whole block): the reflector times 2^64 (dlarfg_scalars_small)
+            T ps[4] = {0, 0, 0, 0}, pk2[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+                if (NG * r + NG - 1 > J) {
+                    vi[r] *= DLARFG_UP;
+                    ps[r & 3] += vi[r] * vi[r];
+                    pk2[r & 3] += vi[r] * a[r];
+                }
+            dlarfg_scalars_small(alpha, group_sum<NG>((ps[0] + ps[1]) + (ps[2] + ps[3])), beta, tau, scale);
+            sk = group_sum<NG>((pk2[0] + pk2[1]) + (pk2[2] + pk2[3]));
+            if (k == J) {
+#pragma unroll
+                for (int r = 0; r < RPT; ++r) a[r] *= DLARFG_UP;
+            }
         }
         const T f = tau * (aJk + sk * scale);  // tau v^T A[:, k]
         if constexpr (INLOOP) {

@@ -120,3 +120,72 @@ def test_update_matches_oracle(hip_ctx, m, D, noise):
     np.testing.assert_allclose(K, wK, rtol=1e-7, atol=1e-10 * np.abs(wK).max())
     np.testing.assert_allclose(C_new @ C_new.T, wC @ wC.T, rtol=1e-9, atol=1e-11 * np.abs(wC @ wC.T).max())
     assert np.all(np.triu(C_new, 1) == 0) and np.all(np.diag(C_new) >= 0)
+
+
+# ---- graded and scaled input: the columnwise backward-error bound of Householder QR ---------------------------------
+def _assert_columnwise(R, A, tol):
+    """|(R^T R - A^T A)_ij| <= tol |a_i| |a_j|: independent of the conditioning and of the grading of A's columns."""
+    nrm = np.linalg.norm(A, axis=0)
+    E = np.abs(R.T @ R - A.T @ A)
+    bound = tol * np.outer(nrm, nrm)
+    assert np.all(E <= bound), f"worst ratio {np.max(E / np.where(bound > 0, bound, np.inf)):.3g}, zero-norm entries {E[bound == 0].max(initial=0)}"
+
+
+def _graded(rows, cols):
+    """Columns graded from 1 down to 1e-12 (the filter's stacked matrices span ~1e-10 .. 1e3)."""
+    A = np.random.default_rng(rows * 7 + cols).standard_normal((rows, cols))
+    return A * np.logspace(0, -12, cols)[None, :]
+
+
+@pytest.mark.parametrize("rows,cols", [(255, 31), (256, 32), (257, 33), (1000, 33), (1003, 64)])
+def test_qr_r_graded_columns(hip_ctx, rows, cols):
+    """Crossing the 32-column panel and the 256-row chunk boundaries.  The standard-normal test above asserts against
+    1e-11 max|R|, under which a column of norm 1e-10 could be wrong altogether; here every entry is held to its own columns."""
+    A = _graded(rows, cols)
+    R = hip_ctx.qr_r(A)
+    assert np.all(np.tril(R, -1) == 0) and np.all(np.diag(R) >= 0)
+    _assert_columnwise(R, A, 1e-14 * np.sqrt(rows))
+
+
+@pytest.mark.parametrize("rows,cols", [(257, 33), (1000, 33)])
+@pytest.mark.parametrize("e", [-300, 300])
+def test_qr_r_power_of_two_scaling_is_exact(hip_ctx, rows, cols, e):
+    """R(2^e A) = 2^e R(A) bit for bit: no absolute threshold anywhere in the fp64 QR, and no underflow or overflow of
+    its intermediate products at 2^+-300 (entries down to 1e-12 2^-300, squares ~1e-205)."""
+    A = _graded(rows, cols)
+    R = hip_ctx.qr_r(A)
+    Rs = hip_ctx.qr_r(np.ldexp(A, e))
+    assert np.array_equal(Rs, np.ldexp(R, e))
+    _assert_columnwise(np.ldexp(Rs, -e), A, 1e-14 * np.sqrt(rows))
+
+
+def _step_pre_arrays(N, steps):
+    """The stacked matrices of both QRs of a step (white.py:114, :120), from the oracle after `steps` steps at N, nu = 2:
+    [(A Cl)^T; Ql^T] (propagate_cholesky_factor) and update_sqrt's block matrix."""
+    from helpers import make_pair
+
+    dt = 2.0 ** -7
+    _, _, opde, osolver = make_pair(N, 2, dt, steps + 1)
+    state = osolver.initialize(opde)
+    for _ in range(steps):
+        state, _ = osolver.attempt_step(state, dt, opde)
+    P, Pinv = osolver.iwp.nordsieck_preconditioner(dt)
+    A, Ql = osolver.iwp.preconditioned_discretize
+    Cl = Pinv @ state.y.cov_sqrtm
+    pre1 = np.vstack(((A @ Cl).T, Ql.T))
+    Clp = o.propagate_cholesky_factor(A @ Cl, Ql)
+    mp = A @ (Pinv @ state.y.mean.reshape((-1,), order="F"))
+    _, H, E = osolver.evaluate_ode(opde, osolver.E0 @ P, osolver.E1 @ P, mp, state.t + dt)
+    m, D = H.shape
+    bottomleft = np.zeros((m, D))
+    bottomleft[:, :m] = E
+    pre2 = np.block([[Clp.T @ H.T, Clp.T], [bottomleft.T, np.zeros((D, D))]])
+    return pre1, pre2
+
+
+@pytest.mark.parametrize("N", [64, 256])
+def test_qr_r_on_the_filter_step_matrices(hip_ctx, N):
+    for M in _step_pre_arrays(N, 2):
+        R = hip_ctx.qr_r(M)
+        assert np.all(np.tril(R, -1) == 0) and np.all(np.diag(R) >= 0)
+        _assert_columnwise(R, M, 1e-14 * np.sqrt(M.shape[0]))
