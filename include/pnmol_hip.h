@@ -25,6 +25,7 @@
  *     `pnmol_filter_steps_begin`.  The handle stays valid after a refused destroy; call it again once the children are gone.
  *   - `pnmol_abi_version()` = 3 (1: before `pnmol_filter_desc.dtype`, the lifetime rule and `pnmol_filter_sweep_layout`;
  *     2: `pnmol_sqrt_filter_create` refused `dtype = 1`, which now selects the fp32 QR of include/pnmol_sqrt.h).
+ *     `pnmol_smoother_step` was added within version 3: a backwards-compatible addition, nothing existing changed.
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -166,6 +167,17 @@ typedef struct pnmol_step_out {
  * `error_estimate_d` (d) optional: dt * sqrt(diag Sq) * sigma (white.py:117-129). */
 int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_state* out,
                       pnmol_step_out* info, double* error_estimate_d);
+
+/* One backward step of the RTS smoother (kalman.py:33-46 / :49-66 of the reference, covariance form):
+ * out = smoothed state at filt_k->t from the filtered state at t_k, the smoothed state at t_k + dt and the step dt the
+ * forward pass took.  States of the same fp64 white-noise filter; out may not alias either input; inputs unchanged.
+ * In the Nordsieck frame of dt (inputs in any frame): P- = A P A^T + Q, G = P A^T (P-)^-1, ms = m + G (ms' - A m),
+ * Ps = P + G (Ps' - P-) G^T with the prior alone (Q uncalibrated, like the filter's covariances); `out` is an ordinary
+ * state in that frame.  -1: bad argument (also a latent-force or fp32 filter), -3: P- not positive definite (pivot in
+ * `pnmol_last_error`), -4: out of memory.  Workspace (~5 Dp^2 doubles) is allocated on the first call and kept by the
+ * filter; one stream synchronisation per call. */
+int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                        pnmol_state* out);
 
 /* k steps of constant dt with no host synchronisation in between -- the loop body of
  * `PDEFilter.solution_generator` under `step.Constant` (pdefilter.py:140-160,

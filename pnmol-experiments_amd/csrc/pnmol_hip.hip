@@ -3541,7 +3541,12 @@ struct pnmol_filter {
     };
     std::vector<GraphEntry> graphs;
     int graph_chunk = 10;  // steps per captured graph (even); 0 disables graphs
-
+    // RTS smoother (pnmol_smoother_step), allocated on first use: the sweep's tall matrices [P-; P A^T; 0; I] -> [L; V; 0; T]
+    // ((3 Dp/32 + 1) * 32 x Dp), its L_jj^-1 tiles, feed tiles and flags, and G, C, Ps^h (Dp x Dp), [m^h | dm] (2 Dp)
+    double *sm_G = nullptr, *sm_F = nullptr, *sm_Linv = nullptr, *sm_hs = nullptr, *sm_gain = nullptr, *sm_C = nullptr,
+           *sm_Psh = nullptr, *sm_vec = nullptr;
+    int *sm_flags = nullptr, *sm_info = nullptr;
+    int sm_nflags = 0;
 };
 
 struct pnmol_state {
@@ -3922,6 +3927,69 @@ int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
     return 0;
 }
 
+// ---- RTS smoother (pnmol_smoother_step; kernels in pnmol_smooth.hip) --------------------------------------------------
+// The tall matrix of the backward step has the error model's layout with Dp columns: [P- (cb); P A^T (cb); zero block; I (cb)],
+// so the forward step's sweep launch factorises it as it is (strict pivots: P- >= Q1 (x) K is positive definite; the padded
+// points carry a unit pivot).
+void free_smoother_ws(pnmol_filter* f) {
+    for (void* p : {(void*)f->sm_G, (void*)f->sm_F, (void*)f->sm_Linv, (void*)f->sm_hs, (void*)f->sm_gain, (void*)f->sm_C,
+                    (void*)f->sm_Psh, (void*)f->sm_vec, (void*)f->sm_flags, (void*)f->sm_info})
+        if (p) (void)hipFree(p);
+    f->sm_G = f->sm_F = f->sm_Linv = f->sm_hs = f->sm_gain = f->sm_C = f->sm_Psh = f->sm_vec = nullptr;
+    f->sm_flags = f->sm_info = nullptr;
+}
+
+int ensure_smoother_ws(pnmol_filter* f) {
+    if (f->sm_G) return 0;
+    pnmol_ctx* ctx = f->ctx;
+    const long Dp = f->Dp;
+    const int cb = (int)(Dp / NB), rt = 3 * cb + 1;
+    const size_t tall = (size_t)rt * NB * Dp, sq = (size_t)Dp * Dp;
+    f->sm_nflags = std::max(rt + cb + 1 + cb * cb, rl_flags(rt, cb).total);
+    hipError_t e = hipSuccess;
+    auto al = [&](void** p, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(p, bytes);
+    };
+    al((void**)&f->sm_G, sizeof(double) * tall);
+    al((void**)&f->sm_F, sizeof(double) * tall);
+    al((void**)&f->sm_Linv, sizeof(double) * (size_t)cb * NB * NB);
+    al((void**)&f->sm_hs, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
+    al((void**)&f->sm_gain, sizeof(double) * sq);
+    al((void**)&f->sm_C, sizeof(double) * sq);
+    al((void**)&f->sm_Psh, sizeof(double) * sq);
+    al((void**)&f->sm_vec, sizeof(double) * 2 * (size_t)Dp);
+    al((void**)&f->sm_flags, sizeof(int) * (size_t)f->sm_nflags);
+    al((void**)&f->sm_info, sizeof(int));
+    if (e == hipSuccess && !f->one) {
+        al((void**)&f->one, sizeof(int));
+        al((void**)&f->info_err, sizeof(int));
+        const int h1 = 1;
+        if (e == hipSuccess) e = hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice);
+    }
+    // (the zero block and the identity rows of sm_G, and the parts of sm_F / sm_Linv the sweep never writes, stay as set here)
+    if (e == hipSuccess) e = hipMemsetAsync(f->sm_G, 0, sizeof(double) * tall, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->sm_F, 0, sizeof(double) * tall, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->sm_Linv, 0, sizeof(double) * (size_t)cb * NB * NB, ctx->stream);
+    if (e == hipSuccess) {
+        k_set_identity<<<(unsigned)((Dp + 255) / 256), 256, 0, ctx->stream>>>(f->sm_G + (2 * Dp + NB) * Dp, (int)Dp);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        ctx->err = std::string("pnmol_smoother_step: workspace: ") + hipGetErrorString(e);
+        free_smoother_ws(f);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    return 0;
+}
+
+template <int N>
+void run_smoother_sweep(pnmol_filter* f) {
+    const int cb = (int)(f->Dp / NB), rt = 3 * cb + 1;
+    DowndateArgs dd{};
+    launch_sweep<N, false>(rt, f->ctx->stream, f->sm_G, f->sm_F, f->sm_Linv, (int)f->Dp, cb, rt, f->sm_flags, f->sm_info, f->one,
+                           dd, f->sm_flags + rt + cb + 1, f->sm_hs, 0, f->xcd_home);
+}
+
 }  // namespace
 
 extern "C" {
@@ -4297,6 +4365,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     if (f->ev_op) hipEventDestroy(f->ev_op);
     for (void* q : {(void*)f->ell_col_base, (void*)f->ell_val_base, (void*)f->ell_diag_slot})
         if (q) hipFree(q);
+    free_smoother_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -4795,6 +4864,66 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
     }
     if (o.info >= 0) {
         ctx->err = "innovation matrix not positive definite at pivot " + std::to_string(o.info);
+        return -3;
+    }
+    return 0;
+}
+
+int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                        pnmol_state* out) {
+    if (!f || !filt_k || !smooth_next || !out || out == filt_k || out == smooth_next || filt_k->f != f || smooth_next->f != f ||
+        out->f != f || !(dt > 0.0) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = "pnmol_smoother_step: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int rc_ws = ensure_smoother_ws(f);
+    if (rc_ws != 0) return rc_ws;
+    // everything in the Nordsieck frame of dt: ts / tsn move the two inputs there (as k_predict's IwpConsts.ts)
+    SmoothConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+    for (int a = 0; a < f->n; ++a) {
+        const double sh = nordsieck_scale(f->nu, a, dt);
+        c.ts[a] = (filt_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, filt_k->frame_dt)) / sh;
+        c.tsn[a] = (smooth_next->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, smooth_next->frame_dt)) / sh;
+    }
+    const long Dp = f->Dp;
+    double *mh = f->sm_vec, *dm = f->sm_vec + Dp;
+    int rc = pnmol_smooth_launch_build(st, f->n, filt_k->P, smooth_next->P, filt_k->mean, smooth_next->mean, f->Kg, c, f->d, f->dp,
+                                       f->sm_G, out->P, f->sm_Psh, mh, dm);
+    if (rc != 0) {
+        ctx->err = "pnmol_smoother_step: kernel launch failed";
+        return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(f->sm_flags, 0, sizeof(int) * f->sm_nflags, st));
+    HIPCHK(ctx, hipMemsetAsync(f->sm_info, 0x7f, sizeof(int), st));
+    switch (f->n) {
+        case 2: run_smoother_sweep<2>(f); break;
+        case 3: run_smoother_sweep<3>(f); break;
+        case 4: run_smoother_sweep<4>(f); break;
+    }
+    const double* V = f->sm_F + Dp * Dp;
+    const double* T = f->sm_F + (2 * Dp + NB) * Dp;
+    rc = pnmol_smooth_launch_finish(st, Dp, V, T, f->sm_Psh, mh, dm, f->sm_gain, f->sm_C, out->P, out->mean, out->var);
+    if (rc != 0) {
+        ctx->err = "pnmol_smoother_step: kernel launch failed";
+        return rc;
+    }
+    int inf = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&inf, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    out->t = filt_k->t;
+    out->frame_dt = dt;
+    if (inf == -2) {
+        ctx->err = "pnmol_smoother_step: a dependency wait of the sweep timed out";
+        return -2;
+    }
+    if (inf < Dp) {
+        ctx->err = "pnmol_smoother_step: predicted covariance not positive definite at pivot " + std::to_string(inf);
         return -3;
     }
     return 0;

@@ -74,6 +74,7 @@ SYMBOLS = {
     "pnmol_state_get_cov": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_state_get_marginal_var": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_filter_step": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp, ctypes.POINTER(StepOut), _c_double_p]),
+    "pnmol_smoother_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "pnmol_filter_steps": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p,
                                           ctypes.POINTER(StepOut)]),
     "pnmol_filter_steps_begin": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double]),
@@ -334,6 +335,13 @@ class Filter:
                                         _dp(err) if want_error else None)
         self.ctx.check(rc, "pnmol_filter_step")
         return out, info, err
+
+    def smoother_step(self, filt_k, smooth_next, dt):
+        """One RTS backward step on the device (`pnmol_smoother_step`): a new State, the smoothed state at filt_k.t."""
+        out = State(self)
+        rc = self.lib.pnmol_smoother_step(self.handle, filt_k.handle, smooth_next.handle, float(dt), out.handle)
+        self.ctx.check(rc, "pnmol_smoother_step")
+        return out
 
     def steps(self, state, k, dt, want_means=True, want_stds=True):
         means = np.empty((k, self.d)) if want_means else None

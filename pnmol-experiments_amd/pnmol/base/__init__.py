@@ -1,3 +1,3 @@
-"""Auxiliary pieces: IWP prior, random variables (reference: src/pnmol/base/)."""
+"""Auxiliary pieces: IWP prior, random variables, filtering and smoothing steps (reference: src/pnmol/base/)."""
 
-from . import iwp, rv, sqrt, stacked_ssm  # noqa: F401
+from . import iwp, kalman, rv, sqrt, stacked_ssm  # noqa: F401

@@ -302,6 +302,37 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                                          diffusion_squared_local=sig[-1] if sig else [])
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
 
+    # ------------------------------------------------------------------ smoothing
+    def smooth(self, solution):
+        """Rauch-Tung-Striebel smoothing of a `solve()` result (kalman.py:33-46 of the reference, covariance form).
+
+        Walks `solution`'s device-resident states backwards, one `pnmol_smoother_step` per step, with the filter that owns
+        them (a later `solve()` / re-bind of this solver does not matter).  The backward pass uses the prior alone (the
+        linearisation of a semilinear solver enters only through the filtered states).  Returns a `PDESolution` with the
+        same `t`, `info` and `diffusion_squared_calibrated`, the smoothed `mean` and device-resident states, so
+        `marginal_std` and `cov_sqrtm` work as for the filter -- and, like them, uncalibrated.  `solution` is unchanged.
+        Supported: fp64 white-noise solvers (pnmol.white), constant and adaptive steps."""
+        from . import latent, sqrtform
+
+        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
+            raise TypeError(f"smooth() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+        ys = list(solution._ys)
+        if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
+            raise TypeError("smooth() needs the device-resident states of this package's solve()")
+        flt = ys[-1].device_state.filter
+        if any(y.device_state.filter is not flt for y in ys):
+            raise ValueError("smooth(): the states of the solution belong to different device filters")
+        t = np.asarray(solution.t)
+        nxt = ys[-1].device_state.clone()                       # terminal state: the filtered one
+        out = [rv.DeviceMultivariateNormal(np.array(ys[-1].mean), nxt)]
+        for k in range(len(ys) - 2, -1, -1):
+            nxt = flt.smoother_step(ys[k].device_state, nxt, t[k + 1] - t[k])
+            out.append(rv.DeviceMultivariateNormal(nxt.mean(), nxt))
+        out.reverse()
+        return pdefilter.PDESolution(t=solution.t, mean=np.stack([y.mean for y in out]), ys=out, info=solution.info,
+                                     diffusion_squared_calibrated=solution.diffusion_squared_calibrated)
+
 
 class LinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
     """EK1 for linear PDEs u_t = L u (white.py:169-186): H = [E1 - L E0 ; B E0], no shift."""
