@@ -20,12 +20,13 @@
  *     ctxs are independent (one thread or process per GPU).
  *   - Lifetimes: a handle keeps its parent alive.  Destroy in the order states -> filter(s) -> ctx.  A destroy call on
  *     a parent that still has live children does NOTHING and returns -1 (`pnmol_last_error` says how many children are
- *     left): `pnmol_filter_destroy` while any `pnmol_state` of the filter lives, `pnmol_ctx_destroy` while any
+ *     left): `pnmol_filter_destroy` while any `pnmol_state` or `pnmol_samples` of the filter lives, `pnmol_ctx_destroy` while any
  *     `pnmol_filter` / `pnmol_sqrt_filter` of the ctx lives, `pnmol_state_destroy` of the target of an unfinished
  *     `pnmol_filter_steps_begin`.  The handle stays valid after a refused destroy; call it again once the children are gone.
  *   - `pnmol_abi_version()` = 3 (1: before `pnmol_filter_desc.dtype`, the lifetime rule and `pnmol_filter_sweep_layout`;
  *     2: `pnmol_sqrt_filter_create` refused `dtype = 1`, which now selects the fp32 QR of include/pnmol_sqrt.h).
- *     `pnmol_smoother_step` was added within version 3: a backwards-compatible addition, nothing existing changed.
+ *     `pnmol_smoother_step` and the joint draws (`pnmol_samples_*`, `pnmol_sample_noise`) were added within version 3:
+ *     backwards-compatible additions, nothing existing changed.
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -40,6 +41,7 @@ extern "C" {
 typedef struct pnmol_ctx pnmol_ctx;
 typedef struct pnmol_filter pnmol_filter; /* model + workspace: L, B, E, R, Gamma, nu       */
 typedef struct pnmol_state pnmol_state;   /* device-resident (mean, covariance, t)          */
+typedef struct pnmol_samples pnmol_samples; /* S joint draws at one time point, device-resident */
 
 /* library / device ----------------------------------------------------------------- */
 int pnmol_abi_version(void);
@@ -178,6 +180,56 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
  * filter; one stream synchronisation per call. */
 int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
                         pnmol_state* out);
+
+/* Joint draws of whole trajectories from the smoothing posterior ----------------------------------------------------------------
+ * The posterior over the trajectory factorises backwards (the chain behind kalman.py:33-46 of the reference): in the Nordsieck
+ * frame of the step dt, A = A1 (x) I, Q = Q1 (x) K (prior only, uncalibrated, as in `pnmol_smoother_step`),
+ *     x_T ~ N(m_T, P_T),    x_k | x_{k+1} ~ N(m_k + G_k (x_{k+1} - A m_k), P_k - G_k P-_k G_k^T),   G_k = P_k A^T (P-_k)^-1.
+ * A backward step draws from it by Matheron's rule, with C C^T = P_k and Gamma_Q = chol(Q1) (x) Gamma:
+ *     xt = m_k + scale C xi_1,     x_k = xt + G_k (x_{k+1} - A xt - scale Gamma_Q xi_2),     xi_1, xi_2 ~ N(0, I_D).
+ * `scale` = 1 draws from the posterior the states carry; scale = sqrt(calibrated diffusion) draws from the calibrated one (the
+ * gain does not depend on the covariance scale).  C is the sweep's Cholesky factor with the dropped-pivot rule of
+ * `pnmol_state_get_cov_sqrtm` (noise-free Dirichlet nodes give zero columns), after every entry of P_k has been held to
+ * |P_ij| <= sqrt(P_ii P_jj) (no change to a PSD matrix; removes rounding noise around zero variances); P- >= Q is factorised strictly.  The gain is not
+ * formed: the step runs the smoother's sweep [P-; P A^T; 0; I] -> [L; V; 0; L^-T] and applies V (L^-1 r) as two thin products.
+ *
+ * A `pnmol_samples` holds S draws at one time, as a device-resident (Dp x Sp) block in the frame of the last step taken
+ * (converted on read-out, like a state); Sp = S rounded up to 64.  It keeps its filter alive exactly as a state does.  Memory:
+ * 6 Dp Sp + 2 S D doubles per block; per filter, on the first draw, 2 Dp^2 doubles (P^h and its factor) + dp^2 (Gamma), and on
+ * the first backward step the smoother's workspace (~9 Dp^2 doubles, shared with `pnmol_smoother_step`).  num_samples is
+ * limited by memory only.
+ *
+ * Noise: `xi` is a host buffer of standard normals, one row per draw: (S, D) for `pnmol_samples_draw`, (S, 2D) for
+ * `pnmol_samples_step_back` (xi_1 in the first D columns, xi_2 in the last D).  Column c of xi_1 is input c of the factor C,
+ * which is computed in the F-flattened order (index j*n + a, the order of `pnmol_state_get_cov_sqrtm`); column a*d + j of xi_2
+ * drives derivative a at mesh point j of Gamma_Q.  Which direction of the state a column moves depends on the factors: only
+ * the distribution of the result is contract.  xi = NULL: generated on the device, nothing crosses the bus.
+ *
+ * Generator (`xi` = NULL, and `pnmol_sample_noise`): Philox4x32-10 (Salmon et al., SC'11) + Box-Muller in fp64.  For draw i
+ * (row) and the pair of columns (2p, 2p+1): counter = (p, i, step_index & 0xffffffff, step_index >> 32), key = (seed &
+ * 0xffffffff, seed >> 32), output words w0..w3;  u1 = ((w0 + 2^32 (w1 & 0xfffff)) + 1/2) 2^-52,  u2 = the same of (w2, w3)
+ * (52 bits, exactly representable, inside (0, 1): no log(0));  column 2p = sqrt(-2 ln u1) cospi(2 u2), column 2p+1 =
+ * sqrt(-2 ln u1) sinpi(2 u2).  So a value depends on (seed, step_index, i, column) only: the same arguments give the same bits,
+ * the first 8 of 64 draws are the 8 draws of an 8-draw block, different seeds / step indices are independent streams.
+ *
+ * Errors: -1 null handles, a latent-force (d_state = 2d) or fp32 filter, a state of another filter, dt <= 0, num_samples < 1,
+ * non-finite scale, `step_back` / `get` on a block that holds no draw, `step_back` whose filt_k->t + dt differs from the
+ * block's time by more than 16 ulp (steps out of order); -3 / -4 / -2 as in `pnmol_smoother_step` (after -2 / -3 the block
+ * holds no draw).  One stream synchronisation per call (the pivot check; `pnmol_samples_draw` has one too, for the NaN check of
+ * its factor).  The input states are never modified. */
+int pnmol_samples_create(pnmol_filter* f, int num_samples, pnmol_samples** out);
+int pnmol_samples_destroy(pnmol_samples* x);
+/* x <- m + scale C xi, C C^T = cov(s): the terminal draw (usable on any state of the filter, e.g. a smoothed one); the block
+ * takes the state's time and frame.  xi_SD (S, D) or NULL (device generator with (seed, step_index)). */
+int pnmol_samples_draw(pnmol_samples* x, const pnmol_state* s, const double* xi_SD, unsigned long long seed,
+                       unsigned long long step_index, double scale);
+/* One backward step, in place: x holds draws at filt_k->t + dt on entry and at filt_k->t on return.  xi_S2D (S, 2D) or NULL. */
+int pnmol_samples_step_back(pnmol_samples* x, const pnmol_state* filt_k, double dt, const double* xi_S2D,
+                            unsigned long long seed, unsigned long long step_index, double scale);
+int pnmol_samples_get(const pnmol_samples* x, double* x_Snd); /* (S, n, d) row-major, raw coordinates */
+int pnmol_samples_get_time(const pnmol_samples* x, double* t);
+/* The device generator by itself: out (rows, cols) row-major = what a NULL xi of that shape would have used. */
+int pnmol_sample_noise(pnmol_ctx* ctx, unsigned long long seed, unsigned long long step_index, int rows, int cols, double* out);
 
 /* k steps of constant dt with no host synchronisation in between -- the loop body of
  * `PDEFilter.solution_generator` under `step.Constant` (pdefilter.py:140-160,

@@ -3547,6 +3547,18 @@ struct pnmol_filter {
            *sm_Psh = nullptr, *sm_vec = nullptr;
     int *sm_flags = nullptr, *sm_info = nullptr;
     int sm_nflags = 0;
+    // Joint draws (pnmol_samples_*), allocated on first use: the square lenient sweep P^h -> C (sp_Gc, sp_F: Dp x Dp, its
+    // L_jj^-1 tiles, feed tiles, flags, info word), Gamma (dp x dp, from the host copy kept at creation) and m^h (Dp).  The
+    // main sweep of a backward step runs in the smoother's workspace above.
+    double *sp_Gc = nullptr, *sp_F = nullptr, *sp_Linv = nullptr, *sp_hs = nullptr, *sp_Gamma = nullptr, *sp_mh = nullptr;
+    int *sp_flags = nullptr, *sp_info = nullptr;
+    int sp_nflags = 0;
+    // a backward step has two independent sweeps (P^h -> C and [P-; P A^T; 0; I]): on wide problems the second one runs on
+    // this side stream, between the two events, while the ctx stream factorises P^h and forms xt and r
+    hipStream_t sp_stream = nullptr;
+    hipEvent_t sp_ev_built = nullptr, sp_ev_swept = nullptr;
+    std::vector<double> hGamma;        // desc->Gamma padded to dp x dp (white-noise fp64 filters)
+    std::atomic<int> samples{0};       // live pnmol_samples objects of this filter (pnmol_filter_destroy refuses while > 0)
 };
 
 struct pnmol_state {
@@ -3556,6 +3568,19 @@ struct pnmol_state {
     double* var = nullptr;   // Dp   marginal variances, same frame as P
     double t = 0.0;
     double frame_dt = 0.0;  // 0 = raw coordinates, else Nordsieck frame of that dt
+};
+
+struct pnmol_samples {
+    pnmol_filter* f = nullptr;
+    int S = 0, Sp = 0;       // draws, padded to a multiple of 64
+    double* X = nullptr;     // Dp x Sp: the draws at time t, in the frame frame_dt
+    double* Xi = nullptr;    // 2 Dp x Sp: noise [xi_1; xi_2]
+    double* Xt = nullptr;    // Dp x Sp: xt = m + s C xi_1
+    double* R = nullptr;     // Dp x Sp: Gamma xi_2 per derivative block, then T^T r
+    double* Y = nullptr;     // Dp x Sp: r
+    double* stage = nullptr; // S x 2D: host-supplied noise / read-out, allocated on first use
+    double t = 0.0, frame_dt = 0.0;
+    bool drawn = false;
 };
 
 namespace {
@@ -3983,11 +4008,103 @@ int ensure_smoother_ws(pnmol_filter* f) {
 }
 
 template <int N>
-void run_smoother_sweep(pnmol_filter* f) {
+void run_smoother_sweep(pnmol_filter* f, hipStream_t st = nullptr) {
     const int cb = (int)(f->Dp / NB), rt = 3 * cb + 1;
     DowndateArgs dd{};
-    launch_sweep<N, false>(rt, f->ctx->stream, f->sm_G, f->sm_F, f->sm_Linv, (int)f->Dp, cb, rt, f->sm_flags, f->sm_info, f->one,
+    launch_sweep<N, false>(rt, st ? st : f->ctx->stream, f->sm_G, f->sm_F, f->sm_Linv, (int)f->Dp, cb, rt, f->sm_flags, f->sm_info, f->one,
                            dd, f->sm_flags + rt + cb + 1, f->sm_hs, 0, f->xcd_home);
+}
+
+// ---- joint draws (pnmol_samples_*; kernels in pnmol_sample.hip) ----------------------------------------------------------
+void free_sampler_ws(pnmol_filter* f) {
+    for (void* p : {(void*)f->sp_Gc, (void*)f->sp_F, (void*)f->sp_Linv, (void*)f->sp_hs, (void*)f->sp_Gamma, (void*)f->sp_mh,
+                    (void*)f->sp_flags, (void*)f->sp_info})
+        if (p) (void)hipFree(p);
+    f->sp_Gc = f->sp_F = f->sp_Linv = f->sp_hs = f->sp_Gamma = f->sp_mh = nullptr;
+    f->sp_flags = f->sp_info = nullptr;
+    if (f->sp_ev_built) (void)hipEventDestroy(f->sp_ev_built);
+    if (f->sp_ev_swept) (void)hipEventDestroy(f->sp_ev_swept);
+    if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
+    f->sp_ev_built = f->sp_ev_swept = nullptr;
+    f->sp_stream = nullptr;
+}
+
+int ensure_sampler_ws(pnmol_filter* f, const char* who) {
+    if (f->sp_Gc) return 0;
+    pnmol_ctx* ctx = f->ctx;
+    const long Dp = f->Dp;
+    const int cb = (int)(Dp / NB);
+    const size_t sq = (size_t)Dp * Dp, gq = (size_t)f->dp * f->dp;
+    f->sp_nflags = std::max(2 * cb + 1 + cb * cb, rl_flags(cb, cb).total);
+    hipError_t e = hipSuccess;
+    auto al = [&](void** p, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(p, bytes);
+    };
+    al((void**)&f->sp_Gc, sizeof(double) * sq);
+    al((void**)&f->sp_F, sizeof(double) * sq);
+    al((void**)&f->sp_Linv, sizeof(double) * (size_t)cb * NB * NB);
+    al((void**)&f->sp_hs, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
+    al((void**)&f->sp_Gamma, sizeof(double) * gq);
+    al((void**)&f->sp_mh, sizeof(double) * (size_t)Dp);
+    al((void**)&f->sp_flags, sizeof(int) * (size_t)f->sp_nflags);
+    al((void**)&f->sp_info, sizeof(int));
+    if (e == hipSuccess && !f->one) {
+        al((void**)&f->one, sizeof(int));
+        al((void**)&f->info_err, sizeof(int));
+        const int h1 = 1;
+        if (e == hipSuccess) e = hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice);
+    }
+    // (the tiles of sp_F above the diagonal and the parts of sp_Linv the sweep never writes stay as set here)
+    if (e == hipSuccess) e = hipMemsetAsync(f->sp_F, 0, sizeof(double) * sq, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->sp_Linv, 0, sizeof(double) * (size_t)cb * NB * NB, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(f->sp_Gamma, f->hGamma.data(), sizeof(double) * gq, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->sp_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->sp_ev_built, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->sp_ev_swept, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        ctx->err = std::string(who) + ": workspace: " + hipGetErrorString(e);
+        free_sampler_ws(f);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    return 0;
+}
+
+// P^h (in sp_Gc) -> C (in sp_F), dropped-pivot rule of pnmol_state_get_cov_sqrtm
+template <int N>
+void run_sampler_factor_sweep(pnmol_filter* f) {
+    const int cb = (int)(f->Dp / NB);
+    DowndateArgs dd{};
+    launch_sweep<N, false>(cb, f->ctx->stream, f->sp_Gc, f->sp_F, f->sp_Linv, (int)f->Dp, cb, cb, f->sp_flags, f->sp_info, f->one,
+                           dd, f->sp_flags + 2 * cb + 1, f->sp_hs, 1, f->xcd_home);
+}
+
+int enqueue_sampler_factor(pnmol_filter* f, const char* who) {
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipMemsetAsync(f->sp_flags, 0, sizeof(int) * f->sp_nflags, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(f->sp_info, 0x7f, sizeof(int), ctx->stream));
+    switch (f->n) {
+        case 2: run_sampler_factor_sweep<2>(f); break;
+        case 3: run_sampler_factor_sweep<3>(f); break;
+        case 4: run_sampler_factor_sweep<4>(f); break;
+        default: ctx->err = std::string(who) + ": unsupported number of derivatives"; return -1;
+    }
+    return 0;
+}
+
+// the noise block of a call: host-supplied (rows of `cols` components) or generated on the device
+int fill_noise(pnmol_samples* x, const double* xi, int cols, unsigned long long seed, unsigned long long step_index, const char* who) {
+    pnmol_filter* f = x->f;
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (xi) {
+        HIPCHK(ctx, hipMemcpyAsync(x->stage, xi, sizeof(double) * (size_t)x->S * cols, hipMemcpyHostToDevice, st));
+        rc = pnmol_sample_launch_scatter(st, x->stage, x->S, cols, f->d, f->dp, f->n, x->Sp, x->Xi);
+    } else {
+        rc = pnmol_sample_launch_noise(st, seed, step_index, x->S, cols, f->d, f->dp, f->n, x->Sp, x->Xi, nullptr);
+    }
+    if (rc != 0) ctx->err = std::string(who) + ": kernel launch failed";
+    return rc;
 }
 
 }  // namespace
@@ -4223,6 +4340,12 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
             Kg[(size_t)i * dp + k] = Kg[(size_t)k * dp + i] = s;
         }
 
+    if (ds == d) {  // (pnmol_samples_step_back draws the process noise with Gamma_Q = chol(Q1) (x) Gamma)
+        f->hGamma.assign((size_t)dp * dp, 0.0);
+        for (int i = 0; i < d; ++i)
+            for (int k = 0; k <= i; ++k) f->hGamma[(size_t)i * dp + k] = desc->Gamma[(size_t)i * d + k];
+    }
+
     auto fail = [&](int code) {
         pnmol_filter_destroy(f);
         return code;
@@ -4350,6 +4473,10 @@ int pnmol_filter_destroy(pnmol_filter* f) {
         f->ctx->err = "pnmol_filter_destroy: " + std::to_string(f->states.load()) + " state(s) of this filter are still alive";
         return -1;
     }
+    if (f->samples.load() != 0) {
+        f->ctx->err = "pnmol_filter_destroy: " + std::to_string(f->samples.load()) + " sample block(s) of this filter are still alive";
+        return -1;
+    }
     if (f->counted) live_rl_filters[f->ctx->device % MAX_DEVICES].fetch_sub(1);
     if (f->registered) f->ctx->children.fetch_sub(1);
     hipSetDevice(f->ctx->device);
@@ -4366,6 +4493,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     for (void* q : {(void*)f->ell_col_base, (void*)f->ell_val_base, (void*)f->ell_diag_slot})
         if (q) hipFree(q);
     free_smoother_ws(f);
+    free_sampler_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -4552,9 +4680,11 @@ int pnmol_state_create(pnmol_filter* f, pnmol_state** out) {
         pnmol_state_destroy(s);
         return -4;
     }
-    hipMemset(s->mean, 0, sizeof(double) * Dp);
-    hipMemset(s->var, 0, sizeof(double) * Dp);
-    hipMemset(s->P, 0, f->psz * Dp * Dp);
+    // (on the ctx stream, which is non-blocking: a memset on the null stream is not ordered against the kernels that write
+    // this state next, and with a second stream alive in the process it has been seen to land after them)
+    hipMemsetAsync(s->mean, 0, sizeof(double) * Dp, ctx->stream);
+    hipMemsetAsync(s->var, 0, sizeof(double) * Dp, ctx->stream);
+    hipMemsetAsync(s->P, 0, f->psz * Dp * Dp, ctx->stream);
     *out = s;
     return 0;
 }
@@ -4925,6 +5055,249 @@ int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_
     if (inf < Dp) {
         ctx->err = "pnmol_smoother_step: predicted covariance not positive definite at pivot " + std::to_string(inf);
         return -3;
+    }
+    return 0;
+}
+
+// ---- joint posterior draws ---------------------------------------------------------------------------------------------
+int pnmol_samples_create(pnmol_filter* f, int num_samples, pnmol_samples** out) {
+    if (out) *out = nullptr;
+    if (!f || !out || num_samples < 1 || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = "pnmol_samples_create: bad argument (null, num_samples < 1, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pnmol_samples* x = new pnmol_samples();
+    x->f = f;
+    x->S = num_samples;
+    x->Sp = round_up(num_samples, 64);
+    f->samples.fetch_add(1);
+    const size_t blk = sizeof(double) * (size_t)f->Dp * x->Sp;
+    const size_t D = (size_t)f->n * f->d;
+    hipError_t e = hipMalloc(&x->X, blk);
+    if (e == hipSuccess) e = hipMalloc(&x->Xi, 2 * blk);
+    if (e == hipSuccess) e = hipMalloc(&x->Xt, blk);
+    if (e == hipSuccess) e = hipMalloc(&x->R, blk);
+    if (e == hipSuccess) e = hipMalloc(&x->Y, blk);
+    if (e == hipSuccess) e = hipMalloc(&x->stage, sizeof(double) * (size_t)x->S * 2 * D);
+    // (on the ctx stream, like pnmol_state_create; the padding rows and columns of the noise are never written again)
+    if (e == hipSuccess) e = hipMemsetAsync(x->X, 0, blk, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->Xi, 0, 2 * blk, ctx->stream);
+    if (e != hipSuccess) {
+        ctx->err = std::string("pnmol_samples_create: ") + hipGetErrorString(e);
+        pnmol_samples_destroy(x);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    *out = x;
+    return 0;
+}
+
+int pnmol_samples_destroy(pnmol_samples* x) {
+    if (!x) return -1;
+    x->f->samples.fetch_sub(1);
+    hipSetDevice(x->f->ctx->device);
+    for (void* p : {(void*)x->X, (void*)x->Xi, (void*)x->Xt, (void*)x->R, (void*)x->Y, (void*)x->stage})
+        if (p) (void)hipFree(p);
+    delete x;
+    return 0;
+}
+
+// the info word(s) of the call's sweep(s): one stream synchronisation
+static int finish_sampler_call(pnmol_filter* f, bool main_sweep, const char* who) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const long Dp = f->Dp;
+    int inf_c = 0, inf_m = 0x7f7f7f7f;
+    HIPCHK(ctx, hipMemcpyAsync(&inf_c, f->sp_info, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (main_sweep) HIPCHK(ctx, hipMemcpyAsync(&inf_m, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    if (inf_c == -2 || inf_m == -2) {
+        ctx->err = std::string(who) + ": a dependency wait of the sweep timed out";
+        return -2;
+    }
+    if (inf_c < Dp) {
+        ctx->err = std::string(who) + ": covariance not positive semi-definite (NaN?) at pivot " + std::to_string(inf_c);
+        return -3;
+    }
+    if (inf_m < Dp) {
+        ctx->err = std::string(who) + ": predicted covariance not positive definite at pivot " + std::to_string(inf_m);
+        return -3;
+    }
+    return 0;
+}
+
+int pnmol_samples_draw(pnmol_samples* x, const pnmol_state* s, const double* xi_SD, unsigned long long seed,
+                       unsigned long long step_index, double scale) {
+    static const char* who = "pnmol_samples_draw";
+    if (!x || !s || s->f != x->f || !std::isfinite(scale)) {
+        if (x) x->f->ctx->err = std::string(who) + ": bad argument (null, state of another filter, non-finite scale)";
+        return -1;
+    }
+    pnmol_filter* f = x->f;
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = ensure_sampler_ws(f, who);
+    if (rc != 0) return rc;
+    x->drawn = false;
+    const long Dp = f->Dp;
+    SampleConsts c{};
+    for (int a = 0; a < f->n; ++a) c.ts[a] = 1.0;  // the draw stays in the state's own frame
+    rc = pnmol_sample_launch_build(st, f->n, s->P, s->mean, f->Kg, c, f->d, f->dp, f->sp_Gc, nullptr, f->sp_mh);
+    if (rc != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return rc;
+    }
+    if ((rc = enqueue_sampler_factor(f, who)) != 0) return rc;
+    if ((rc = fill_noise(x, xi_SD, f->n * f->d, seed, step_index, who)) != 0) return rc;
+    // x = m + scale C xi
+    rc = pnmol_sample_launch_thin(st, f->sp_F, x->Xi, x->X, nullptr, f->sp_mh, scale, Dp, x->Sp, 0, 1, 1, f->n);
+    if (rc != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return rc;
+    }
+    if ((rc = finish_sampler_call(f, false, who)) != 0) return rc;
+    x->t = s->t, x->frame_dt = s->frame_dt, x->drawn = true;
+    return 0;
+}
+
+int pnmol_samples_step_back(pnmol_samples* x, const pnmol_state* filt_k, double dt, const double* xi_S2D,
+                            unsigned long long seed, unsigned long long step_index, double scale) {
+    static const char* who = "pnmol_samples_step_back";
+    if (!x || !filt_k || filt_k->f != x->f || !(dt > 0.0) || !std::isfinite(dt) || !std::isfinite(scale) || !x->drawn) {
+        if (x)
+            x->f->ctx->err = std::string(who) + ": bad argument (null, state of another filter, dt <= 0, non-finite scale, or a "
+                                                "block that holds no draw yet)";
+        return -1;
+    }
+    pnmol_filter* f = x->f;
+    pnmol_ctx* ctx = f->ctx;
+    {
+        const double tn = filt_k->t + dt;
+        const double tol = 16.0 * 2.220446049250313e-16 * std::max({std::fabs(tn), std::fabs(x->t), dt});
+        if (!(std::fabs(tn - x->t) <= tol)) {
+            ctx->err = std::string(who) + ": the block holds draws at t = " + std::to_string(x->t) + ", not at filt_k->t + dt = " +
+                       std::to_string(tn) + " (steps out of order?)";
+            return -1;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = ensure_sampler_ws(f, who);
+    if (rc == 0) rc = ensure_smoother_ws(f);
+    if (rc != 0) return rc;
+    const long Dp = f->Dp;
+    const int Sp = x->Sp;
+    SampleConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+    for (int a = 0; a < f->n; ++a) {  // chol(Q1): n x n, positive definite
+        for (int b = 0; b <= a; ++b) {
+            double v = c.Q1[a * SM_MAXN + b];
+            for (int e = 0; e < b; ++e) v -= c.Lq[a * SM_MAXN + e] * c.Lq[b * SM_MAXN + e];
+            c.Lq[a * SM_MAXN + b] = (a == b) ? std::sqrt(v) : v / c.Lq[b * SM_MAXN + b];
+        }
+        const double sh = nordsieck_scale(f->nu, a, dt);
+        c.ts[a] = (filt_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, filt_k->frame_dt)) / sh;
+        c.tsn[a] = (x->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, x->frame_dt)) / sh;
+    }
+    auto failed = [&](int code) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        x->drawn = false;  // the block may be half written
+        if (f->sp_stream) (void)hipStreamSynchronize(f->sp_stream);  // (nothing of this call may outlive it)
+        return code;
+    };
+    // C_k sweep -> xt, r -> main sweep -> V (T^T r)
+    rc = pnmol_sample_launch_build(st, f->n, filt_k->P, filt_k->mean, f->Kg, c, f->d, f->dp, f->sp_Gc, f->sm_G, f->sp_mh);
+    if (rc != 0) return failed(rc);
+    // The main sweep needs nothing of what follows on the ctx stream before `T^T r`.  Where both sweeps are the left-looking
+    // kernel (more than 17 column blocks; its workgroups wait for earlier-dispatched ones of their own launch only, so two
+    // launches in flight cannot block each other) it runs beside the factorisation of P^h; the register-resident kernel of
+    // the small problems wants its workgroups co-resident and stays in line.
+    const bool beside = Dp / NB > 17 || !sweep_rl_enabled();
+    hipStream_t sw = beside ? f->sp_stream : st;
+    auto main_sweep = [&]() -> int {
+        HIPCHK(ctx, hipMemsetAsync(f->sm_flags, 0, sizeof(int) * f->sm_nflags, sw));
+        HIPCHK(ctx, hipMemsetAsync(f->sm_info, 0x7f, sizeof(int), sw));
+        switch (f->n) {
+            case 2: run_smoother_sweep<2>(f, sw); break;
+            case 3: run_smoother_sweep<3>(f, sw); break;
+            case 4: run_smoother_sweep<4>(f, sw); break;
+        }
+        return 0;
+    };
+    if (beside) {
+        HIPCHK(ctx, hipEventRecord(f->sp_ev_built, st));
+        HIPCHK(ctx, hipStreamWaitEvent(sw, f->sp_ev_built, 0));
+        if ((rc = main_sweep()) != 0) return rc;
+        HIPCHK(ctx, hipEventRecord(f->sp_ev_swept, sw));
+    }
+    if ((rc = enqueue_sampler_factor(f, who)) != 0) return rc;
+    if ((rc = fill_noise(x, xi_S2D, 2 * f->n * f->d, seed, step_index, who)) != 0) return rc;
+    rc = pnmol_sample_launch_thin(st, f->sp_F, x->Xi, x->Xt, nullptr, f->sp_mh, scale, Dp, Sp, 0, 1, 1, f->n);  // xt = m^h + s C xi_1
+    if (rc == 0) rc = pnmol_sample_launch_thin(st, f->sp_Gamma, x->Xi + Dp * Sp, x->R, nullptr, nullptr, 1.0, f->dp, Sp, 0, 1, f->n, 0);
+    if (rc == 0) rc = pnmol_sample_launch_resid(st, f->n, c, scale, f->dp, Sp, x->X, x->Xt, x->R, x->Y);
+    if (rc != 0) return failed(rc);
+    if (beside) HIPCHK(ctx, hipStreamWaitEvent(st, f->sp_ev_swept, 0));
+    else if ((rc = main_sweep()) != 0) return rc;
+    const double* V = f->sm_F + Dp * Dp;
+    const double* T = f->sm_F + (2 * Dp + NB) * Dp;
+    rc = pnmol_sample_launch_thin(st, T, x->Y, x->R, nullptr, nullptr, 1.0, Dp, Sp, 1, 1, 1, 0);        // y = T^T r = L^-1 r
+    if (rc == 0) rc = pnmol_sample_launch_thin(st, V, x->R, x->X, x->Xt, nullptr, 1.0, Dp, Sp, 0, 0, 1, 0);  // x = xt + V y
+    if (rc != 0) return failed(rc);
+    x->drawn = false;
+    if ((rc = finish_sampler_call(f, true, who)) != 0) return rc;
+    x->t = filt_k->t, x->frame_dt = dt, x->drawn = true;
+    return 0;
+}
+
+int pnmol_samples_get(const pnmol_samples* x, double* x_Snd) {
+    if (!x || !x_Snd || !x->drawn) {
+        if (x) x->f->ctx->err = "pnmol_samples_get: bad argument (null, or a block that holds no draw)";
+        return -1;
+    }
+    pnmol_filter* f = x->f;
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double sc[MAXN];
+    for (int a = 0; a < f->n; ++a) sc[a] = x->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, x->frame_dt);
+    if (pnmol_sample_launch_get(ctx->stream, f->n, f->d, f->dp, x->Sp, x->S, sc, x->X, x->stage) != 0) {
+        ctx->err = "pnmol_samples_get: kernel launch failed";
+        return -2;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(x_Snd, x->stage, sizeof(double) * (size_t)x->S * f->n * f->d, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int pnmol_samples_get_time(const pnmol_samples* x, double* t) {
+    if (!x || !t || !x->drawn) return -1;
+    *t = x->t;
+    return 0;
+}
+
+int pnmol_sample_noise(pnmol_ctx* ctx, unsigned long long seed, unsigned long long step_index, int rows, int cols, double* out) {
+    if (!ctx || !out || rows < 1 || cols < 1) {
+        if (ctx) ctx->err = "pnmol_sample_noise: bad argument";
+        return -1;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double* dev = nullptr;
+    const size_t bytes = sizeof(double) * (size_t)rows * cols;
+    hipError_t e = hipMalloc(&dev, bytes);
+    if (e != hipSuccess) {
+        ctx->err = std::string("pnmol_sample_noise: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    int rc = pnmol_sample_launch_noise(ctx->stream, seed, step_index, rows, cols, 1, 1, 1, 0, nullptr, dev);
+    if (rc == 0) e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (rc == 0 && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dev);
+    if (rc != 0 || e != hipSuccess) {
+        ctx->err = std::string("pnmol_sample_noise: ") + (rc != 0 ? "kernel launch failed" : hipGetErrorString(e));
+        return -2;
     }
     return 0;
 }

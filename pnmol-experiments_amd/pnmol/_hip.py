@@ -75,6 +75,15 @@ SYMBOLS = {
     "pnmol_state_get_marginal_var": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_filter_step": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp, ctypes.POINTER(StepOut), _c_double_p]),
     "pnmol_smoother_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
+    "pnmol_samples_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "pnmol_samples_destroy": (ctypes.c_int, [_vp]),
+    "pnmol_samples_draw": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_double]),
+    "pnmol_samples_step_back": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _c_double_p, ctypes.c_ulonglong, ctypes.c_ulonglong,
+                                               ctypes.c_double]),
+    "pnmol_samples_get": (ctypes.c_int, [_vp, _c_double_p]),
+    "pnmol_samples_get_time": (ctypes.c_int, [_vp, _c_double_p]),
+    "pnmol_sample_noise": (ctypes.c_int, [_vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
+                                          _c_double_p]),
     "pnmol_filter_steps": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p,
                                           ctypes.POINTER(StepOut)]),
     "pnmol_filter_steps_begin": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double]),
@@ -233,6 +242,14 @@ class Context:
         self.lib.pnmol_qr_last_ms(ctypes.byref(ms))
         return ms.value
 
+    def sample_noise(self, seed, step_index, rows, cols):
+        """(rows, cols) standard normals of the device generator (`pnmol_sample_noise`): what a draw of `rows` samples with
+        `xi = NULL` uses for (seed, step_index)."""
+        out = np.empty((int(rows), int(cols)))
+        self.check(self.lib.pnmol_sample_noise(self.handle, int(seed), int(step_index), int(rows), int(cols), _dp(out)),
+                   "pnmol_sample_noise")
+        return out
+
     def check(self, rc, what):
         if rc != 0:
             msg = self.lib.pnmol_last_error(self.handle)
@@ -269,6 +286,7 @@ class Filter:
         # cyclic collector clears weakrefs to unreachable objects BEFORE it runs finalisers, so a WeakSet would be empty
         # exactly when a filter and its states die together -- and the states' device buffers would leak.
         self._live = {}
+        self._live_samples = {}     # the same for the pnmol_samples objects (Samples)
 
     def __del__(self):
         # The cyclic garbage collector (and interpreter shutdown) finalises a filter and its states in ANY order: the
@@ -277,6 +295,10 @@ class Filter:
         while live:
             _, sh = live.popitem()
             self.lib.pnmol_state_destroy(sh)
+        live = getattr(self, "_live_samples", None)
+        while live:
+            _, sh = live.popitem()
+            self.lib.pnmol_samples_destroy(sh)
         h, self.handle = getattr(self, "handle", None), None
         if h:
             self.lib.pnmol_filter_destroy(h)
@@ -305,6 +327,10 @@ class Filter:
 
     def new_state(self):
         return State(self)
+
+    def new_samples(self, num_samples):
+        """A device-resident block of `num_samples` joint draws (`pnmol_samples_create`)."""
+        return Samples(self, num_samples)
 
     def predict_mean(self, state_in, dt):
         out = np.empty(self.d)
@@ -453,6 +479,58 @@ class State:
         out = np.empty((D, D))
         self.ctx.check(self.lib.pnmol_state_get_cov(self.handle, _dp(out)), "pnmol_state_get_cov")
         return out
+
+
+class Samples:
+    """`pnmol_samples`: S joint draws of the state at one time point, device-resident; `draw` at the terminal state, then
+    `step_back` through the filtered states in decreasing time."""
+
+    def __init__(self, flt, num_samples):
+        self.filter, self.lib, self.ctx = flt, flt.lib, flt.ctx
+        self.num_samples = int(num_samples)
+        h = _vp()
+        self.ctx.check(self.lib.pnmol_samples_create(flt.handle, self.num_samples, ctypes.byref(h)), "pnmol_samples_create")
+        self.handle = h
+        flt._live_samples[id(self)] = h
+
+    def _destroy(self):
+        h, self.handle = getattr(self, "handle", None), None
+        flt = getattr(self, "filter", None)
+        # (no entry: Filter.__del__ ran first and has destroyed this block's handle already)
+        if h and flt is not None and flt._live_samples.pop(id(self), None) is not None:
+            self.lib.pnmol_samples_destroy(h)
+
+    def __del__(self):
+        self._destroy()
+
+    def _noise(self, xi, cols):
+        return None if xi is None else _f64(xi, (self.num_samples, cols))
+
+    def draw(self, state, xi=None, *, seed=0, step_index=0, scale=1.0):
+        """x <- mean + scale * C xi with C C^T = cov(state) (`pnmol_samples_draw`); xi (S, D) or None (device generator)."""
+        a = self._noise(xi, self.filter.n * self.filter.d)
+        rc = self.lib.pnmol_samples_draw(self.handle, state.handle, None if a is None else _dp(a), int(seed), int(step_index),
+                                         float(scale))
+        self.ctx.check(rc, "pnmol_samples_draw")
+
+    def step_back(self, filt_k, dt, xi=None, *, seed=0, step_index=0, scale=1.0):
+        """One backward step in place (`pnmol_samples_step_back`); xi (S, 2D) or None (device generator)."""
+        a = self._noise(xi, 2 * self.filter.n * self.filter.d)
+        rc = self.lib.pnmol_samples_step_back(self.handle, filt_k.handle, float(dt), None if a is None else _dp(a), int(seed),
+                                              int(step_index), float(scale))
+        self.ctx.check(rc, "pnmol_samples_step_back")
+
+    def get(self):
+        """The draws as (S, n, d), raw coordinates."""
+        out = np.empty((self.num_samples, self.filter.n, self.filter.d))
+        self.ctx.check(self.lib.pnmol_samples_get(self.handle, _dp(out)), "pnmol_samples_get")
+        return out
+
+    @property
+    def t(self):
+        t = ctypes.c_double(0.0)
+        self.ctx.check(self.lib.pnmol_samples_get_time(self.handle, ctypes.byref(t)), "pnmol_samples_get_time")
+        return t.value
 
 
 class SqrtFilter:

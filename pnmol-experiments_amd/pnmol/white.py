@@ -333,6 +333,48 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         return pdefilter.PDESolution(t=solution.t, mean=np.stack([y.mean for y in out]), ys=out, info=solution.info,
                                      diffusion_squared_calibrated=solution.diffusion_squared_calibrated)
 
+    # ------------------------------------------------------------------ joint draws
+    def sample(self, solution, num_samples, *, seed=0, noise=None, calibrated=False):
+        """Joint draws of whole trajectories from the smoothing posterior of a `solve()` result.
+
+        Walks `solution`'s device-resident filtered states backwards, one `pnmol_samples_step_back` per step, with the
+        filter that owns them (a later `solve()` / re-bind of this solver does not matter): x_T ~ N(m_T, P_T), then
+        x_k | x_{k+1} by the backward recursion behind `smooth` (prior alone; include/pnmol_hip.h, "Joint draws").  Returns an
+        array (num_samples, T+1, n, d) in raw coordinates; `[:, :, 0]` are draws of the PDE solution.  The marginals of the
+        draws are those of `smooth(solution)`; what the draws add is the coupling across time.
+
+        noise: None (generated on the device from `seed`, step k using `step_index = k`), or a sequence of T+1 arrays of
+        standard normals, `noise[k]` of shape (S, 2D) for k < T and (S, D) for k = T (D = n d).  calibrated=True draws from
+        the calibrated posterior (noise scale sqrt(solution.diffusion_squared_calibrated)).  `solution` is unchanged.
+        Supported: fp64 white-noise solvers (pnmol.white), constant and adaptive steps."""
+        from . import latent, sqrtform
+
+        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
+            raise TypeError(f"sample() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+        ys = list(solution._ys)
+        if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
+            raise TypeError("sample() needs the device-resident states of this package's solve()")
+        flt = ys[-1].device_state.filter
+        if any(y.device_state.filter is not flt for y in ys):
+            raise ValueError("sample(): the states of the solution belong to different device filters")
+        S, T = int(num_samples), len(ys) - 1
+        if S < 1:
+            raise ValueError(f"sample(): num_samples must be at least 1, got {num_samples}")
+        if noise is not None and len(noise) != T + 1:
+            raise ValueError(f"sample(): noise must have one entry per time point ({T + 1}), got {len(noise)}")
+        scale = float(np.sqrt(solution.diffusion_squared_calibrated)) if calibrated else 1.0
+        t = np.asarray(solution.t)
+        xi = (lambda k: None) if noise is None else (lambda k: noise[k])
+        block = flt.new_samples(S)
+        out = np.empty((S, T + 1, flt.n, flt.d))
+        block.draw(ys[-1].device_state, xi(T), seed=seed, step_index=T, scale=scale)
+        out[:, T] = block.get()
+        for k in range(T - 1, -1, -1):
+            block.step_back(ys[k].device_state, t[k + 1] - t[k], xi(k), seed=seed, step_index=k, scale=scale)
+            out[:, k] = block.get()
+        return out
+
 
 class LinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
     """EK1 for linear PDEs u_t = L u (white.py:169-186): H = [E1 - L E0 ; B E0], no shift."""
