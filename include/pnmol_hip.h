@@ -20,13 +20,14 @@
  *     ctxs are independent (one thread or process per GPU).
  *   - Lifetimes: a handle keeps its parent alive.  Destroy in the order states -> filter(s) -> ctx.  A destroy call on
  *     a parent that still has live children does NOTHING and returns -1 (`pnmol_last_error` says how many children are
- *     left): `pnmol_filter_destroy` while any `pnmol_state` or `pnmol_samples` of the filter lives, `pnmol_ctx_destroy` while any
+ *     left): `pnmol_filter_destroy` while any `pnmol_state`, `pnmol_samples` or `pnmol_bridge` of the filter lives, `pnmol_ctx_destroy` while any
  *     `pnmol_filter` / `pnmol_sqrt_filter` of the ctx lives, `pnmol_state_destroy` of the target of an unfinished
  *     `pnmol_filter_steps_begin`.  The handle stays valid after a refused destroy; call it again once the children are gone.
  *   - `pnmol_abi_version()` = 3 (1: before `pnmol_filter_desc.dtype`, the lifetime rule and `pnmol_filter_sweep_layout`;
  *     2: `pnmol_sqrt_filter_create` refused `dtype = 1`, which now selects the fp32 QR of include/pnmol_sqrt.h).
  *     `pnmol_smoother_step` and the joint draws (`pnmol_samples_*`, `pnmol_sample_noise`) were added within version 3:
- *     backwards-compatible additions, nothing existing changed.
+ *     backwards-compatible additions, nothing existing changed.  So was the dense output (`pnmol_state_predict*`,
+ *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -42,6 +43,7 @@ typedef struct pnmol_ctx pnmol_ctx;
 typedef struct pnmol_filter pnmol_filter; /* model + workspace: L, B, E, R, Gamma, nu       */
 typedef struct pnmol_state pnmol_state;   /* device-resident (mean, covariance, t)          */
 typedef struct pnmol_samples pnmol_samples; /* S joint draws at one time point, device-resident */
+typedef struct pnmol_bridge pnmol_bridge;   /* what dense output inside one step [t_k, t_k + dt] needs, device-resident */
 
 /* library / device ----------------------------------------------------------------- */
 int pnmol_abi_version(void);
@@ -181,6 +183,53 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
 int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
                         pnmol_state* out);
 
+/* Dense output: the posterior BETWEEN grid times ------------------------------------------------------------------------------
+ * Between two grid times there is no measurement, so given the states at the two ends of a step the state at t inside it follows
+ * the bridge of the prior IWP (x) K, under the prior and under every posterior alike.  With h = dt, theta = (t - t_k) / h in (0, 1),
+ * in the Nordsieck frame of h, p_a = nu - a + 1/2:
+ *     A_th[a,b] = A1[a,b] th^(p_a - p_b),   Q_th[a,b] = Q1[a,b] th^(p_a + p_b)      (entry by entry; likewise with 1 - th)
+ *     B+ = Q_th A_(1-th)^T Q1^-1,   B- = (I - B+ A_(1-th)) A_th,   Qb = (I - B+ A_(1-th)) Q_th (.)^T + B+ Q_(1-th) B+^T     (n x n, host)
+ *     x_t | x_k, x_{k+1} ~ N((B- (x) I) x_k + (B+ (x) I) x_{k+1}, Qb (x) K)
+ *     ms_t = (B- (x) I) ms_k + (B+ (x) I) ms_{k+1}
+ *     Ps_t = (B-) Ps_k (B-)^T + (B-) C_k (B+)^T + ((B-) C_k (B+)^T)^T + (B+) Ps_{k+1} (B+)^T + Qb (x) K,     C_k = G_k Ps_{k+1}
+ * (the same coefficients as pnmol/base/iwp.py, `bridge_coefficients`).  C_k is the lag-one cross-covariance the smoother step forms
+ * anyway.  No factorisation is involved: a marginal needs the n x n blocks of Ps_k, C_k, Ps_{k+1} at equal mesh points only.
+ * Like the smoother these entry points use the prior alone (uncalibrated) and serve the fp64 white-noise filters; a latent-force
+ * (d_state = 2d) or fp32 filter gives -1.
+ *
+ * `pnmol_state_predict`: out = N(A m, A P A^T + Q) at in->t + dt, the prior carried over dt > 0 from `in` (any frame, unchanged;
+ * out may not alias it), an ordinary state in the frame of dt.  No measurement, no use of the filter's step buffers or captured
+ * graphs, no synchronisation.  Dense output of a filtering solution, forecasts past the last grid time.
+ * `pnmol_state_predict_marginals`: mean and marginal std of all n derivatives of that prediction for nq step sizes dt_q[i] >= 0
+ * at once (0: the state's own values), (nq, n, d) row-major each, raw coordinates; either output may be NULL.  One gather of the
+ * state's point-diagonal blocks, one evaluation launch, the read-out copied straight into the caller's arrays, one synchronisation.  -1: a negative or non-finite dt_q. */
+int pnmol_state_predict(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_state* out);
+int pnmol_state_predict_marginals(pnmol_filter* f, const pnmol_state* in, int nq, const double* dt_q, double* means_qnd,
+                                  double* stds_qnd);
+/* Exactly `pnmol_smoother_step` (same kernels, `out` bit for bit the same, same errors) that also returns a bridge for the
+ * interval [filt_k->t, filt_k->t + dt].  The bridge owns, in the frame of dt: both smoothed means, the n x n blocks at equal mesh
+ * points of Ps_k, C_k and Ps_{k+1}, diag K ((3 n^2 + 2 n + 1) dp doubles) and, with keep_full != 0, all of C_k (Dp^2 doubles).  It
+ * references no state (it copies what it needs: one small launch, with keep_full one device copy more; the blocks of a filter's
+ * bridges are carved out of device allocations of 64 blocks, each freed when the last bridge in it is destroyed) and keeps its filter alive
+ * exactly as a state does.  On any error *bridge is NULL. */
+int pnmol_smoother_step_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                               pnmol_state* out, int keep_full, pnmol_bridge** bridge);
+int pnmol_bridge_destroy(pnmol_bridge* b);
+int pnmol_bridge_get_interval(const pnmol_bridge* b, double* t, double* dt, int* has_full); /* any output may be NULL */
+/* Mean and marginal std of all n derivatives at nq times inside [t_k, t_k + dt], (nq, n, d) row-major each, raw coordinates
+ * (either output may be NULL): one launch for all queries, the read-out copied straight into the caller's arrays, one
+ * synchronisation.  A time equal to an end point
+ * (16 ulp) returns that end's stored values, not the formula.  Variances are clamped at 0 before the root.  -1: a time outside the
+ * interval or not finite, nq < 1. */
+int pnmol_bridge_eval(const pnmol_bridge* b, int nq, const double* t_q, double* means_qnd, double* stds_qnd);
+/* The full posterior at t_k < t < t_k + dt as an ordinary state in the frame of dt (mean, covariance, marginal variances), so that
+ * `pnmol_state_get_cov`, `_cov_sqrtm`, `pnmol_samples_draw` work on it.  smooth_k / smooth_next: the smoothed states at the two
+ * ends (the `out` and `smooth_next` of the step that made the bridge, in any frame, unchanged; out may alias neither).  One pass
+ * over the three Dp x Dp matrices, symmetric bit for bit; no synchronisation.  -1: a bridge without keep_full, states of another
+ * filter or not at the bridge's two times (16 ulp, the rule of `pnmol_samples_step_back`), t not strictly inside the interval. */
+int pnmol_bridge_state(const pnmol_bridge* b, const pnmol_state* smooth_k, const pnmol_state* smooth_next, double t,
+                       pnmol_state* out);
+
 /* Joint draws of whole trajectories from the smoothing posterior ----------------------------------------------------------------
  * The posterior over the trajectory factorises backwards (the chain behind kalman.py:33-46 of the reference): in the Nordsieck
  * frame of the step dt, A = A1 (x) I, Q = Q1 (x) K (prior only, uncalibrated, as in `pnmol_smoother_step`),
@@ -226,6 +275,23 @@ int pnmol_samples_draw(pnmol_samples* x, const pnmol_state* s, const double* xi_
 /* One backward step, in place: x holds draws at filt_k->t + dt on entry and at filt_k->t on return.  xi_S2D (S, 2D) or NULL. */
 int pnmol_samples_step_back(pnmol_samples* x, const pnmol_state* filt_k, double dt, const double* xi_S2D,
                             unsigned long long seed, unsigned long long step_index, double scale);
+/* Draws BETWEEN (or behind) the times of drawn blocks (dense output, see "Dense output" above).  Given the draws in `left` and
+ * `right`, left->t < t < right->t with no grid time strictly between them, the state at t follows the prior's bridge whatever the
+ * data: in the frame of h = right->t - left->t, theta = (t - left->t) / h,
+ *     x_t = (B- (x) I) x_l + (B+ (x) I) x_r + scale (chol(Qb) (x) Gamma) xi,      xi ~ N(0, I_D),
+ * no posterior quantity enters.  `out` (a block of the same filter and num_samples, aliasing neither input) receives draws at t
+ * that are coupled to those in `left` and `right`; it may itself serve as a neighbour of a further time (several times inside one
+ * interval are NOT independent given its ends: draw them one after the other, each between its nearest drawn neighbours).
+ * right = NULL: the one-sided case, draws carried forwards from `left` by the prior (B- = A1, B+ = 0, Qb = Q1 in the frame of
+ * t - left->t): times beyond the last grid time.  xi_SD (S, D), column a*d + j driving derivative a at mesh point j (as xi_2 of
+ * `pnmol_samples_step_back`), or NULL for the device generator with (seed, step_index).  The Gamma xi product is the batched thin
+ * product of the backward step; the inputs are unchanged.  One stream synchronisation.  -1: null / aliasing / foreign blocks,
+ * different num_samples, a block that holds no draw, t not strictly between the blocks' times, non-finite scale. */
+int pnmol_samples_interpolate(pnmol_samples* out, const pnmol_samples* left, const pnmol_samples* right, double t,
+                              const double* xi_SD, unsigned long long seed, unsigned long long step_index, double scale);
+/* A copy of a block (draws, time, frame): a block has to survive the in-place `pnmol_samples_step_back` that produces its left
+ * neighbour. */
+int pnmol_samples_clone(const pnmol_samples* x, pnmol_samples** out);
 int pnmol_samples_get(const pnmol_samples* x, double* x_Snd); /* (S, n, d) row-major, raw coordinates */
 int pnmol_samples_get_time(const pnmol_samples* x, double* t);
 /* The device generator by itself: out (rows, cols) row-major = what a NULL xi of that shape would have used. */

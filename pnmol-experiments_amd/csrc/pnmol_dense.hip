@@ -1,0 +1,363 @@
+// pnmol_dense.hip -- kernels of the dense output between grid times (`pnmol_bridge_*`, `pnmol_state_predict*`,
+// include/pnmol_hip.h).
+//
+// Between two grid times there is no measurement, so the posterior at t given the two neighbouring states is the bridge of the
+// prior IWP (x) K, whose gains are n x n matrices Kronecker the identity (pnmol/base/iwp.py, bridge_coefficients):
+//     x_t | x_l, x_r ~ N((Bm (x) I) x_l + (Bp (x) I) x_r, Qb (x) K)
+//     Ps_t = Bm Pl Bm^T + Bm C Bp^T + (Bm C Bp^T)^T + Bp Pr Bp^T + Qb (x) K,     C = Cov(x_l, x_r | data)
+// block by block over pairs of mesh points: no factorisation, no product longer than n.  Everything here is element-wise in the
+// mesh points and memory-bound; no MFMA.  Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp,
+// row-major, zero padding (dp is a multiple of 32).
+#include <hip/hip_runtime.h>
+
+#include "pnmol_internal.hpp"
+
+namespace {
+
+// point-diagonal n x n blocks of the three matrices, the two means and diag K: one thread per mesh point
+template <int N>
+__global__ __launch_bounds__(256) void k_dn_gather(const double* __restrict__ Pl, const double* __restrict__ Cx,
+                                                   const double* __restrict__ Pr, const double* __restrict__ ml,
+                                                   const double* __restrict__ mr, const double* __restrict__ Kg, DenseFrames c,
+                                                   int dp, double* __restrict__ blk) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= dp) return;
+    const long Dp = (long)N * dp;
+    double* bl = blk;
+    double* bc = blk + (long)N * N * dp;
+    double* br = blk + 2L * N * N * dp;
+    double* vl = blk + 3L * N * N * dp;
+    double* vr = vl + (long)N * dp;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            const long idx = ((long)a * dp + j) * Dp + (long)b * dp + j;
+            bl[(long)(a * N + b) * dp + j] = c.sl[a] * c.sl[b] * Pl[idx];
+            if (Cx) bc[(long)(a * N + b) * dp + j] = Cx[idx];  // (C is given in the frame of the interval)
+            if (Pr) br[(long)(a * N + b) * dp + j] = c.sr[a] * c.sr[b] * Pr[idx];
+        }
+        vl[(long)a * dp + j] = c.sl[a] * ml[(long)a * dp + j];
+        if (mr) vr[(long)a * dp + j] = c.sr[a] * mr[(long)a * dp + j];
+    }
+    vr[(long)N * dp + j] = Kg[(long)j * dp + j];
+}
+
+// mean and marginal std of every derivative at (query blockIdx.y, mesh point j); the per-query constants are uniform over the
+// workgroup (scalar loads from the table), the stores run along j: rows of the (nq, n, d) outputs
+template <int N>
+__global__ __launch_bounds__(256) void k_dn_eval(const double* __restrict__ blk, const DenseQuery* __restrict__ table, int one_sided,
+                                                 int d, int dp, double* __restrict__ means, double* __restrict__ stds) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int q = blockIdx.y;
+    if (j >= d) return;
+    const DenseQuery& t = table[q];
+    const double* bl = blk;
+    const double* bc = blk + (long)N * N * dp;
+    const double* br = blk + 2L * N * N * dp;
+    const double* vl = blk + 3L * N * N * dp;
+    const double* vr = vl + (long)N * dp;
+    double* mo = means + (long)q * N * d + j;
+    double* so = stds + (long)q * N * d + j;
+    if (t.knot != 0) {  // an end point: its stored values (the order of operations of pnmol_state_get_mean / _marginal_var)
+        const double* v = t.knot == 1 ? vl : vr;
+        const double* p = t.knot == 1 ? bl : br;
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+            mo[(long)a * d] = t.sc[a] * v[(long)a * dp + j];
+            const double var = t.sc[a] * t.sc[a] * p[(long)(a * N + a) * dp + j];
+            so[(long)a * d] = sqrt(fmax(var, 0.0));
+        }
+        return;
+    }
+    const double kjj = vr[(long)N * dp + j];
+    double xl[N], xr[N], pl[N][N], pc[N][N], pr[N][N];
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        xl[a] = vl[(long)a * dp + j];
+        xr[a] = one_sided ? 0.0 : vr[(long)a * dp + j];
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            pl[a][b] = bl[(long)(a * N + b) * dp + j];
+            pc[a][b] = one_sided ? 0.0 : bc[(long)(a * N + b) * dp + j];
+            pr[a][b] = one_sided ? 0.0 : br[(long)(a * N + b) * dp + j];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        double m = 0.0, v = t.qbd[a] * kjj;
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            const double bm = t.Bm[a * SM_MAXN + b], bp = t.Bp[a * SM_MAXN + b];
+            m += bm * xl[b] + bp * xr[b];
+            double ul = 0.0, uc = 0.0, ur = 0.0;  // rows b of Pl Bm^T, C Bp^T, Pr Bp^T at column a
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                ul += pl[b][e] * t.Bm[a * SM_MAXN + e];
+                uc += pc[b][e] * t.Bp[a * SM_MAXN + e];
+                ur += pr[b][e] * t.Bp[a * SM_MAXN + e];
+            }
+            v += bm * (ul + 2.0 * uc) + bp * ur;
+        }
+        mo[(long)a * d] = t.sc[a] * m;
+        so[(long)a * d] = t.sc[a] * sqrt(fmax(v, 0.0));
+    }
+}
+
+// the predict half of the smoother's block transform: Pout = A1 (ts ts^T o P) A1^T + Q1 K, block by block
+template <int N>
+__global__ __launch_bounds__(256) void k_dn_predict(const double* __restrict__ P, const double* __restrict__ Kg, SmoothConsts c,
+                                                    int dp, double* __restrict__ Pout, double* __restrict__ var) {
+    const int k = blockIdx.x * 32 + threadIdx.x;
+    const int j = blockIdx.y * 8 + threadIdx.y;
+    const long Dp = (long)N * dp;
+    double X[N][N], XA[N][N];
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b) X[a][b] = c.ts[a] * c.ts[b] * P[((long)a * dp + j) * Dp + (long)b * dp + k];
+    const double kjk = Kg[(long)j * dp + k];
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            double s = 0.0;
+#pragma unroll
+            for (int e = 0; e < N; ++e) s += X[a][e] * c.A1[b * SM_MAXN + e];
+            XA[a][b] = s;
+        }
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            double s = c.Q1[a * SM_MAXN + b] * kjk;
+#pragma unroll
+            for (int e = 0; e < N; ++e) s += c.A1[a * SM_MAXN + e] * XA[e][b];
+            Pout[((long)a * dp + j) * Dp + (long)b * dp + k] = s;
+            if (a == b && j == k) var[(long)a * dp + j] = s;
+        }
+}
+
+// mout = L1 (sl o ml) [+ L2 (sr o mr)]: the n x n mixes of the derivative rows of one or two mean vectors
+struct MeanMats {
+    double L1[SM_MAXN * SM_MAXN], L2[SM_MAXN * SM_MAXN];
+};
+template <int N>
+__global__ __launch_bounds__(256) void k_dn_mean(const double* __restrict__ ml, const double* __restrict__ mr, MeanMats mm,
+                                                      DenseFrames c, int dp, double* __restrict__ mout) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= dp) return;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            s += mm.L1[a * SM_MAXN + b] * c.sl[b] * ml[(long)b * dp + j];
+            if (mr) s += mm.L2[a * SM_MAXN + b] * c.sr[b] * mr[(long)b * dp + j];
+        }
+        mout[(long)a * dp + j] = s;
+    }
+}
+
+// R += Lm[:, c] (x[:] Rm^T): row c of an n x n operand block X (two neighbouring mesh points k, k+1 per lane) enters Lm X Rm^T
+template <int N>
+__device__ __forceinline__ void mix_row(double2 (&R)[N][N], const double2 (&x)[N], int c, const double* Lm, const double* Rm) {
+#pragma unroll
+    for (int b = 0; b < N; ++b) {
+        double2 t = {0.0, 0.0};
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            t.x += x[e].x * Rm[b * SM_MAXN + e];
+            t.y += x[e].y * Rm[b * SM_MAXN + e];
+        }
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+            R[a][b].x += Lm[a * SM_MAXN + c] * t.x;
+            R[a][b].y += Lm[a * SM_MAXN + c] * t.y;
+        }
+    }
+}
+
+// The full covariance at t.  One workgroup per pair of 32-point tiles (J, K), J >= K; of the symmetric operands Pl, Pr it reads
+// tile (J, K) only, of C the tiles (J, K) and (K, J), the second transposed through LDS (one row of n sub-blocks at a time); it
+// writes tile (J, K) and, through the same LDS buffer, its mirror image (K, J), so that the result is symmetric bit for bit.  On a
+// diagonal tile the entries on or below the diagonal of the (point, derivative) order are the ones that are kept and mirrored.
+// 512 lanes: lane -> row j of the tile and two neighbouring points k (16-byte accesses; the 16 lanes of a row cover its 32 points
+// = two whole 128-byte lines).  A lane holds one n x n block of double2 (32 registers' worth of doubles at n = 4) plus one
+// operand row.
+template <int N>
+__global__ __launch_bounds__(512) void k_dn_state(const double* __restrict__ Pl, const double* __restrict__ Pr,
+                                                  const double* __restrict__ C, const double* __restrict__ Kg, DenseMix c, int dp,
+                                                  double* __restrict__ Pout, double* __restrict__ var) {
+    __shared__ double s[N][32][33];
+    // the five n x n matrices, read as LDS broadcasts inside the loop over operand rows: as 80 uniform registers they do not fit
+    // beside the accumulators (the first form of this kernel spilled 269 registers at n = 4)
+    __shared__ double cm[5 * SM_MAXN * SM_MAXN];
+    const int J = blockIdx.y, K = blockIdx.x;
+    if (K > J) return;
+    const int tid = threadIdx.x, kl = 2 * (tid & 15), jl = tid >> 4;
+    if (tid < 5 * SM_MAXN * SM_MAXN) cm[tid] = reinterpret_cast<const double*>(&c)[tid];
+    const double* cBmS = cm;
+    const double* cBpS = cm + SM_MAXN * SM_MAXN;
+    const double* cBm = cm + 2 * SM_MAXN * SM_MAXN;
+    const double* cBp = cm + 3 * SM_MAXN * SM_MAXN;
+    const long Dp = (long)N * dp;
+    const int j0 = J * 32, k0 = K * 32;
+    const bool diag = J == K;
+    double2 R[N][N];
+    {
+        const double2 kk = *reinterpret_cast<const double2*>(Kg + (long)(j0 + jl) * dp + k0 + kl);
+#pragma unroll
+        for (int a = 0; a < N; ++a)
+#pragma unroll
+            for (int b = 0; b < N; ++b) R[a][b] = double2{c.Qb[a * SM_MAXN + b] * kk.x, c.Qb[a * SM_MAXN + b] * kk.y};
+    }
+#pragma unroll 1
+    for (int cc = 0; cc < N; ++cc) {
+        // sub-blocks (e, cc) of tile (K, J) of C, transposed: s[e][j][k] = C[(e, k0 + k), (cc, j0 + j)]  (this lane: row k = jl of
+        // the source tile, its columns j = kl, kl + 1)
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            const double2 v = *reinterpret_cast<const double2*>(C + ((long)e * dp + k0 + jl) * Dp + (long)cc * dp + j0 + kl);
+            s[e][kl][jl] = v.x;
+            s[e][kl + 1][jl] = v.y;
+        }
+        __syncthreads();
+        const long row = ((long)cc * dp + j0 + jl) * Dp + k0 + kl;
+        double2 x[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) x[e] = *reinterpret_cast<const double2*>(Pl + row + (long)e * dp);
+        mix_row<N>(R, x, cc, cBmS, cBmS);
+#pragma unroll
+        for (int e = 0; e < N; ++e) x[e] = *reinterpret_cast<const double2*>(Pr + row + (long)e * dp);
+        mix_row<N>(R, x, cc, cBpS, cBpS);
+#pragma unroll
+        for (int e = 0; e < N; ++e) x[e] = *reinterpret_cast<const double2*>(C + row + (long)e * dp);
+        mix_row<N>(R, x, cc, cBm, cBp);
+#pragma unroll
+        for (int e = 0; e < N; ++e) x[e] = double2{s[e][jl][kl], s[e][jl][kl + 1]};
+        mix_row<N>(R, x, cc, cBp, cBm);
+    }
+    // tile (J, K)
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            double* p = Pout + ((long)a * dp + j0 + jl) * Dp + (long)b * dp + k0 + kl;
+            if (!diag) {
+                *reinterpret_cast<double2*>(p) = R[a][b];
+            } else {
+                if (jl > kl || (jl == kl && a >= b)) p[0] = R[a][b].x;
+                if (jl > kl + 1 || (jl == kl + 1 && a >= b)) p[1] = R[a][b].y;
+                if (a == b && jl == kl) var[(long)a * dp + j0 + jl] = R[a][a].x;
+                if (a == b && jl == kl + 1) var[(long)a * dp + j0 + jl] = R[a][a].y;
+            }
+        }
+    // its mirror image: entry ((b, k), (a, j)) of the result = R_jk[a][b]
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            s[b][kl][jl] = R[a][b].x;  // s[b][k][j]
+            s[b][kl + 1][jl] = R[a][b].y;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            const int kt = jl, jt = kl;  // target row (b, k0 + kt), columns (a, j0 + jt), (a, j0 + jt + 1)
+            double* p = Pout + ((long)b * dp + k0 + kt) * Dp + (long)a * dp + j0 + jt;
+            const double2 v = {s[b][kt][jt], s[b][kt][jt + 1]};
+            if (!diag) {
+                *reinterpret_cast<double2*>(p) = v;
+            } else {
+                if (jt > kt || (jt == kt && a > b)) p[0] = v.x;
+                if (jt + 1 > kt || (jt + 1 == kt && a > b)) p[1] = v.y;
+            }
+        }
+    }
+}
+
+// out = BmS xl [+ BpS xr] + Ls W, element-wise over (point, draw): the mix of pnmol_samples_interpolate
+template <int N>
+__global__ __launch_bounds__(256) void k_dn_draw_mix(DenseDrawMix c, int dp, int Sp, const double* __restrict__ xl,
+                                                     const double* __restrict__ xr, const double* __restrict__ W,
+                                                     double* __restrict__ out) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const long per = (long)dp * Sp;
+    if (e >= per) return;
+    double l[N], r[N], w[N];
+#pragma unroll
+    for (int a = 0; a < N; ++a) l[a] = xl[a * per + e], r[a] = xr ? xr[a * per + e] : 0.0, w[a] = W[a * per + e];
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            s += c.BmS[a * SM_MAXN + b] * l[b] + c.BpS[a * SM_MAXN + b] * r[b];
+            if (b <= a) s += c.Ls[a * SM_MAXN + b] * w[b];
+        }
+        out[a * per + e] = s;
+    }
+}
+
+}  // namespace
+
+#define DN_SWITCH(n, CALL)          \
+    switch (n) {                    \
+        case 2: { constexpr int N = 2; CALL; } break; \
+        case 3: { constexpr int N = 3; CALL; } break; \
+        case 4: { constexpr int N = 4; CALL; } break; \
+        default: return -1;         \
+    }
+
+int pnmol_dense_launch_gather(hipStream_t st, int n, const double* Pl, const double* Cx, const double* Pr, const double* ml,
+                              const double* mr, const double* Kg, const DenseFrames& c, int dp, double* blk) {
+    const unsigned g = (unsigned)((dp + 255) / 256);
+    DN_SWITCH(n, (k_dn_gather<N><<<g, 256, 0, st>>>(Pl, Cx, Pr, ml, mr, Kg, c, dp, blk)));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int pnmol_dense_launch_eval(hipStream_t st, int n, int d, int dp, int nq, const double* blk, const DenseQuery* table, int one_sided,
+                            double* means, double* stds) {
+    // (gridDim.y is limited to 65535)
+    for (int q0 = 0; q0 < nq; q0 += 65535) {
+        const int nn = nq - q0 < 65535 ? nq - q0 : 65535;
+        const dim3 grid((unsigned)((d + 255) / 256), (unsigned)nn);
+        DN_SWITCH(n, (k_dn_eval<N><<<grid, 256, 0, st>>>(blk, table + q0, one_sided, d, dp, means + (long)q0 * n * d,
+                                                         stds + (long)q0 * n * d)));
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int pnmol_dense_launch_predict(hipStream_t st, int n, const double* P, const double* m, const double* Kg, const SmoothConsts& c,
+                               int dp, double* Pout, double* var, double* mout) {
+    const dim3 grid(dp / 32, dp / 8), blk(32, 8);
+    MeanMats mm{};
+    DenseFrames fr{};
+    for (int a = 0; a < SM_MAXN; ++a) fr.sl[a] = c.ts[a];
+    for (int i = 0; i < SM_MAXN * SM_MAXN; ++i) mm.L1[i] = c.A1[i];
+    DN_SWITCH(n, (k_dn_predict<N><<<grid, blk, 0, st>>>(P, Kg, c, dp, Pout, var),
+                  k_dn_mean<N><<<(unsigned)((dp + 255) / 256), 256, 0, st>>>(m, nullptr, mm, fr, dp, mout)));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int pnmol_dense_launch_state(hipStream_t st, int n, const double* Pl, const double* Pr, const double* C, const double* Kg,
+                             const double* ml, const double* mr, const DenseMix& c, int dp, double* Pout, double* var, double* mout) {
+    const dim3 grid(dp / 32, dp / 32);
+    MeanMats mm{};
+    DenseFrames fr{};
+    for (int a = 0; a < SM_MAXN; ++a) fr.sl[a] = fr.sr[a] = 1.0;  // (the bridge's means are in the frame of the interval)
+    for (int i = 0; i < SM_MAXN * SM_MAXN; ++i) mm.L1[i] = c.Bm[i], mm.L2[i] = c.Bp[i];
+    DN_SWITCH(n, (k_dn_state<N><<<grid, 512, 0, st>>>(Pl, Pr, C, Kg, c, dp, Pout, var),
+                  k_dn_mean<N><<<(unsigned)((dp + 255) / 256), 256, 0, st>>>(ml, mr, mm, fr, dp, mout)));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int pnmol_dense_launch_draw_mix(hipStream_t st, int n, const DenseDrawMix& c, int dp, int Sp, const double* xl, const double* xr,
+                                const double* W, double* out) {
+    const unsigned grid = (unsigned)(((long)dp * Sp + 255) / 256);
+    DN_SWITCH(n, (k_dn_draw_mix<N><<<grid, 256, 0, st>>>(c, dp, Sp, xl, xr, W, out)));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}

@@ -3559,6 +3559,11 @@ struct pnmol_filter {
     hipEvent_t sp_ev_built = nullptr, sp_ev_swept = nullptr;
     std::vector<double> hGamma;        // desc->Gamma padded to dp x dp (white-noise fp64 filters)
     std::atomic<int> samples{0};       // live pnmol_samples objects of this filter (pnmol_filter_destroy refuses while > 0)
+    // Dense output (pnmol_bridge_*, pnmol_state_predict_marginals): scratch for the query table and the read-out, grown on demand
+    std::atomic<int> bridges{0};       // live pnmol_bridge objects of this filter (pnmol_filter_destroy refuses while > 0)
+    void* dn_scratch = nullptr;
+    size_t dn_cap = 0;
+    struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
 };
 
 struct pnmol_state {
@@ -3568,6 +3573,24 @@ struct pnmol_state {
     double* var = nullptr;   // Dp   marginal variances, same frame as P
     double t = 0.0;
     double frame_dt = 0.0;  // 0 = raw coordinates, else Nordsieck frame of that dt
+};
+
+// The blocks of a filter's bridges come out of slabs of BRIDGE_SLAB_SLOTS blocks: smooth() makes one bridge per step, and a device
+// allocation per step is what the bridges would otherwise cost most.  A slab is freed when the last bridge in it is destroyed (the
+// filter's current slab is reused instead while it has free slots).
+constexpr int BRIDGE_SLAB_SLOTS = 64;
+struct BridgeSlab {
+    double* base = nullptr;
+    int used = 0;  // slots handed out
+    int live = 0;  // bridges alive
+};
+
+struct pnmol_bridge {
+    pnmol_filter* f = nullptr;
+    BridgeSlab* slab = nullptr;
+    double* blk = nullptr;    // point-diagonal blocks of Ps_k, C_k, Ps_{k+1}, the two means, diag K (pnmol_dense_block_doubles): a slot of slab
+    double* Cfull = nullptr;  // C_k (Dp x Dp), kept on request
+    double t = 0.0, dt = 0.0; // the interval [t, t + dt]; everything above is in the Nordsieck frame of dt
 };
 
 struct pnmol_samples {
@@ -4477,10 +4500,19 @@ int pnmol_filter_destroy(pnmol_filter* f) {
         f->ctx->err = "pnmol_filter_destroy: " + std::to_string(f->samples.load()) + " sample block(s) of this filter are still alive";
         return -1;
     }
+    if (f->bridges.load() != 0) {
+        f->ctx->err = "pnmol_filter_destroy: " + std::to_string(f->bridges.load()) + " bridge(s) of this filter are still alive";
+        return -1;
+    }
     if (f->counted) live_rl_filters[f->ctx->device % MAX_DEVICES].fetch_sub(1);
     if (f->registered) f->ctx->children.fetch_sub(1);
     hipSetDevice(f->ctx->device);
     drop_graphs(f);
+    if (f->dn_scratch) hipFree(f->dn_scratch);
+    if (f->dn_slab) {  // (no bridge is alive: the slab is empty)
+        if (f->dn_slab->base) hipFree(f->dn_slab->base);
+        delete f->dn_slab;
+    }
     if (f->ctr) hipFree(f->ctr);
     if (f->h_pin) hipHostFree(f->h_pin);
     void* ptrs[] = {f->ell_col, f->ell_val, f->Kg,   f->rdiag,   f->Rdense, f->shift,     f->G,        f->F,
@@ -4999,8 +5031,77 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
     return 0;
 }
 
-int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
-                        pnmol_state* out) {
+// the tail of a smoother step: the sweep's info word, one stream synchronisation
+static int smoother_step_wait(pnmol_filter* f, const pnmol_state* filt_k, double dt, pnmol_state* out) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const long Dp = f->Dp;
+    int inf = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&inf, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    out->t = filt_k->t;
+    out->frame_dt = dt;
+    if (inf == -2) {
+        ctx->err = "pnmol_smoother_step: a dependency wait of the sweep timed out";
+        return -2;
+    }
+    if (inf < Dp) {
+        ctx->err = "pnmol_smoother_step: predicted covariance not positive definite at pivot " + std::to_string(inf);
+        return -3;
+    }
+    return 0;
+}
+
+// What a query inside [t_k, t_k + dt] needs, copied out of the step's own buffers (enqueued behind the step, before the next one
+// reuses them): the point-diagonal blocks of Ps_k (out), C_k = G Ps^h (sm_C) and Ps^h_{k+1} (the product k_sm_build formed), the
+// two means, diag K; with keep_full all of C_k.  On failure nothing is left behind and *bridge is NULL.
+static int make_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt, const pnmol_state* out,
+                       const double* tsn, int keep_full, pnmol_bridge** bridge) {
+    static const char* who = "pnmol_smoother_step_bridge";
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t sq = (size_t)f->Dp * f->Dp;
+    pnmol_bridge* br = new pnmol_bridge();
+    br->f = f, br->t = filt_k->t, br->dt = dt;
+    f->bridges.fetch_add(1);
+    auto fail = [&](int code, const std::string& why) {
+        ctx->err = std::string(who) + ": " + why;
+        (void)hipStreamSynchronize(st);
+        pnmol_bridge_destroy(br);
+        return code;
+    };
+    const size_t slot = pnmol_dense_block_doubles(f->n, f->dp);
+    hipError_t e = hipSuccess;
+    if (!f->dn_slab || f->dn_slab->used == BRIDGE_SLAB_SLOTS) {  // (a full slab now belongs to its bridges alone)
+        BridgeSlab* sl = new BridgeSlab();
+        e = hipMalloc(&sl->base, sizeof(double) * slot * BRIDGE_SLAB_SLOTS);
+        if (e == hipSuccess) f->dn_slab = sl;
+        else delete sl;
+    }
+    if (e == hipSuccess) {
+        br->slab = f->dn_slab;
+        br->blk = br->slab->base + slot * br->slab->used;
+        br->slab->used += 1, br->slab->live += 1;
+        if (keep_full) e = hipMalloc(&br->Cfull, sizeof(double) * sq);
+    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? -4 : -2, hipGetErrorString(e));
+    DenseFrames fr{};
+    for (int a = 0; a < f->n; ++a) fr.sl[a] = 1.0, fr.sr[a] = tsn[a];
+    if (pnmol_dense_launch_gather(st, f->n, out->P, f->sm_C, smooth_next->P, out->mean, smooth_next->mean, f->Kg, fr, f->dp,
+                                  br->blk) != 0)
+        return fail(-2, "kernel launch failed");
+    if (keep_full) {
+        e = hipMemcpyAsync(br->Cfull, f->sm_C, sizeof(double) * sq, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return fail(-2, hipGetErrorString(e));
+    }
+    *bridge = br;
+    return 0;
+}
+
+static int smoother_step_impl(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                              pnmol_state* out, int keep_full, pnmol_bridge** bridge) {
+    if (bridge) *bridge = nullptr;
     if (!f || !filt_k || !smooth_next || !out || out == filt_k || out == smooth_next || filt_k->f != f || smooth_next->f != f ||
         out->f != f || !(dt > 0.0) || f->ds != f->d || f->p32) {
         if (f) f->ctx->err = "pnmol_smoother_step: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
@@ -5042,20 +5143,312 @@ int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_
         ctx->err = "pnmol_smoother_step: kernel launch failed";
         return rc;
     }
-    int inf = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&inf, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipGetLastError());
-    out->t = filt_k->t;
-    out->frame_dt = dt;
-    if (inf == -2) {
-        ctx->err = "pnmol_smoother_step: a dependency wait of the sweep timed out";
+    if (bridge) {
+        rc = make_bridge(f, filt_k, smooth_next, dt, out, c.tsn, keep_full, bridge);
+        if (rc != 0) return rc;
+    }
+    rc = smoother_step_wait(f, filt_k, dt, out);
+    if (rc != 0 && bridge && *bridge) {
+        pnmol_bridge_destroy(*bridge);
+        *bridge = nullptr;
+    }
+    return rc;
+}
+
+int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                        pnmol_state* out) {
+    return smoother_step_impl(f, filt_k, smooth_next, dt, out, 0, nullptr);
+}
+
+// ---- dense output between grid times (kernels in pnmol_dense.hip) ----------------------------------------------------------
+int pnmol_smoother_step_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                               pnmol_state* out, int keep_full, pnmol_bridge** bridge) {
+    if (!bridge) {
+        if (f) f->ctx->err = "pnmol_smoother_step_bridge: bad argument (null bridge pointer)";
+        return -1;
+    }
+    return smoother_step_impl(f, filt_k, smooth_next, dt, out, keep_full, bridge);
+}
+
+int pnmol_bridge_destroy(pnmol_bridge* b) {
+    if (!b) return -1;
+    b->f->bridges.fetch_sub(1);
+    hipSetDevice(b->f->ctx->device);
+    if (BridgeSlab* sl = b->slab) {
+        sl->live -= 1;
+        if (sl->live == 0) {
+            if (sl == b->f->dn_slab && sl->used < BRIDGE_SLAB_SLOTS) {
+                sl->used = 0;  // (readers and the next writer of a block are on the ctx stream: ordered)
+            } else {
+                if (sl == b->f->dn_slab) b->f->dn_slab = nullptr;
+                (void)hipFree(sl->base);
+                delete sl;
+            }
+        }
+    }
+    if (b->Cfull) (void)hipFree(b->Cfull);
+    delete b;
+    return 0;
+}
+
+int pnmol_bridge_get_interval(const pnmol_bridge* b, double* t, double* dt, int* has_full) {
+    if (!b) return -1;
+    if (t) *t = b->t;
+    if (dt) *dt = b->dt;
+    if (has_full) *has_full = b->Cfull != nullptr;
+    return 0;
+}
+
+namespace {
+
+// (A_th, Q_th): the IWP over the fraction th of a step, in the Nordsieck frame of the whole step (pnmol/base/iwp.py,
+// _partial_interval): entry by entry, every exponent that meets a non-zero entry is >= 0
+void partial_interval(const pnmol_filter* f, double th, double* A, double* Q) {
+    for (int a = 0; a < f->n; ++a)
+        for (int b = 0; b < f->n; ++b) {
+            A[a * MAXN + b] = b >= a ? f->iwp.A1[a * MAXN + b] * std::pow(th, b - a) : 0.0;
+            Q[a * MAXN + b] = f->iwp.Q1[a * MAXN + b] * std::pow(th, 2 * f->nu + 1 - a - b);
+        }
+}
+
+// pnmol/base/iwp.py, bridge_coefficients: Bp = Q_th A_c^T Q1^-1, M = I - Bp A_c, Bm = M A_th, Qb = M Q_th M^T + Bp Q_c Bp^T
+void bridge_coefficients(const pnmol_filter* f, double th, double* Bm, double* Bp, double* Qb) {
+    const int n = f->n;
+    double A[MAXN * MAXN], Q[MAXN * MAXN], Ac[MAXN * MAXN], Qc[MAXN * MAXN], L[MAXN * MAXN] = {0}, M[MAXN * MAXN];
+    partial_interval(f, th, A, Q);
+    partial_interval(f, 1.0 - th, Ac, Qc);
+    for (int a = 0; a < n; ++a)  // chol(Q1): n x n, positive definite (cond <= 1.6e4 at n = 4)
+        for (int b = 0; b <= a; ++b) {
+            double v = f->iwp.Q1[a * MAXN + b];
+            for (int e = 0; e < b; ++e) v -= L[a * MAXN + e] * L[b * MAXN + e];
+            L[a * MAXN + b] = (a == b) ? std::sqrt(v) : v / L[b * MAXN + b];
+        }
+    for (int col = 0; col < n; ++col) {  // column col of X = Q1^-1 (A_c Q_th); Bp = X^T
+        double y[MAXN];
+        for (int a = 0; a < n; ++a) {
+            double v = 0.0;
+            for (int e = 0; e < n; ++e) v += Ac[a * MAXN + e] * Q[e * MAXN + col];
+            y[a] = v;
+        }
+        for (int a = 0; a < n; ++a) {
+            for (int e = 0; e < a; ++e) y[a] -= L[a * MAXN + e] * y[e];
+            y[a] /= L[a * MAXN + a];
+        }
+        for (int a = n - 1; a >= 0; --a) {
+            for (int e = a + 1; e < n; ++e) y[a] -= L[e * MAXN + a] * y[e];
+            y[a] /= L[a * MAXN + a];
+        }
+        for (int a = 0; a < n; ++a) Bp[col * MAXN + a] = y[a];
+    }
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            double v = a == b ? 1.0 : 0.0;
+            for (int e = 0; e < n; ++e) v -= Bp[a * MAXN + e] * Ac[e * MAXN + b];
+            M[a * MAXN + b] = v;
+        }
+    double MQ[MAXN * MAXN], BQ[MAXN * MAXN];
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            double v = 0.0, w = 0.0, u = 0.0;
+            for (int e = 0; e < n; ++e) {
+                v += M[a * MAXN + e] * A[e * MAXN + b];
+                w += M[a * MAXN + e] * Q[e * MAXN + b];
+                u += Bp[a * MAXN + e] * Qc[e * MAXN + b];
+            }
+            Bm[a * MAXN + b] = v, MQ[a * MAXN + b] = w, BQ[a * MAXN + b] = u;
+        }
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            double v = 0.0;
+            for (int e = 0; e < n; ++e) v += MQ[a * MAXN + e] * M[b * MAXN + e] + BQ[a * MAXN + e] * Bp[b * MAXN + e];
+            Qb[a * MAXN + b] = Qb[b * MAXN + a] = v;
+        }
+}
+
+int ensure_dense_scratch(pnmol_filter* f, size_t bytes, const char* who) {
+    if (bytes <= f->dn_cap) return 0;
+    if (f->dn_scratch) (void)hipFree(f->dn_scratch);
+    f->dn_scratch = nullptr, f->dn_cap = 0;
+    const hipError_t e = hipMalloc(&f->dn_scratch, bytes);
+    if (e != hipSuccess) {
+        f->ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    f->dn_cap = bytes;
+    return 0;
+}
+
+inline bool times_agree(double a, double b, double dt) {  // the rule of pnmol_samples_step_back
+    return std::fabs(a - b) <= 16.0 * 2.220446049250313e-16 * std::max({std::fabs(a), std::fabs(b), std::fabs(dt)});
+}
+
+// table -> device, one launch, the read-out: means / stds (nq, n, d)
+int run_dense_eval(pnmol_filter* f, const double* blk_dev, bool blk_in_scratch, const std::vector<DenseQuery>& table, int one_sided,
+                   double* means, double* stds, const char* who) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t nq = table.size(), no = nq * (size_t)f->n * f->d;
+    const size_t blk_bytes = blk_in_scratch ? sizeof(double) * pnmol_dense_block_doubles(f->n, f->dp) : 0;
+    char* base = static_cast<char*>(f->dn_scratch);
+    double* out_dev = reinterpret_cast<double*>(base + blk_bytes);
+    DenseQuery* tab_dev = reinterpret_cast<DenseQuery*>(base + blk_bytes + 2 * no * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(tab_dev, table.data(), sizeof(DenseQuery) * nq, hipMemcpyHostToDevice, st));
+    if (pnmol_dense_launch_eval(st, f->n, f->d, f->dp, (int)nq, blk_dev, tab_dev, one_sided, out_dev, out_dev + no) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
         return -2;
     }
-    if (inf < Dp) {
-        ctx->err = "pnmol_smoother_step: predicted covariance not positive definite at pivot " + std::to_string(inf);
-        return -3;
+    // straight into the caller's arrays (no host staging: at 10 000 queries the read-out is 123 MB), one synchronisation
+    if (means) HIPCHK(ctx, hipMemcpyAsync(means, out_dev, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (stds) HIPCHK(ctx, hipMemcpyAsync(stds, out_dev + no, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
+int pnmol_bridge_eval(const pnmol_bridge* b, int nq, const double* t_q, double* means_qnd, double* stds_qnd) {
+    static const char* who = "pnmol_bridge_eval";
+    if (!b || nq < 1 || !t_q || (!means_qnd && !stds_qnd)) {
+        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, nq < 1)";
+        return -1;
     }
+    pnmol_filter* f = b->f;
+    pnmol_ctx* ctx = f->ctx;
+    std::vector<DenseQuery> table((size_t)nq);
+    for (int q = 0; q < nq; ++q) {
+        const double t = t_q[q];
+        const bool at_l = times_agree(t, b->t, b->dt), at_r = times_agree(t, b->t + b->dt, b->dt);
+        if (!std::isfinite(t) || (!at_l && !at_r && !(t > b->t && t < b->t + b->dt))) {
+            ctx->err = std::string(who) + ": query time " + std::to_string(t) + " is not inside the bridge's interval [" +
+                       std::to_string(b->t) + ", " + std::to_string(b->t + b->dt) + "]";
+            return -1;
+        }
+        DenseQuery& e = table[(size_t)q];
+        std::memset(&e, 0, sizeof(e));
+        for (int a = 0; a < f->n; ++a) e.sc[a] = nordsieck_scale(f->nu, a, b->dt);
+        const double th = (t - b->t) / b->dt;
+        e.knot = (at_l || !(th > 0.0)) ? 1 : ((at_r || !(th < 1.0)) ? 2 : 0);
+        if (e.knot == 0) {
+            double Qb[MAXN * MAXN];
+            bridge_coefficients(f, th, e.Bm, e.Bp, Qb);
+            for (int a = 0; a < f->n; ++a) e.qbd[a] = Qb[a * MAXN + a];
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t no = (size_t)nq * f->n * f->d;
+    int rc = ensure_dense_scratch(f, 2 * no * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
+    if (rc != 0) return rc;
+    return run_dense_eval(f, b->blk, false, table, 0, means_qnd, stds_qnd, who);
+}
+
+int pnmol_state_predict(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_state* out) {
+    if (!f || !in || !out || in == out || in->f != f || out->f != f || !(dt > 0.0) || !std::isfinite(dt) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = "pnmol_state_predict: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SmoothConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+    for (int a = 0; a < f->n; ++a)
+        c.ts[a] = (in->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, in->frame_dt)) / nordsieck_scale(f->nu, a, dt);
+    if (pnmol_dense_launch_predict(ctx->stream, f->n, in->P, in->mean, f->Kg, c, f->dp, out->P, out->var, out->mean) != 0) {
+        ctx->err = "pnmol_state_predict: kernel launch failed";
+        return -2;
+    }
+    out->t = in->t + dt;
+    out->frame_dt = dt;
+    return 0;
+}
+
+int pnmol_state_predict_marginals(pnmol_filter* f, const pnmol_state* in, int nq, const double* dt_q, double* means_qnd,
+                                  double* stds_qnd) {
+    static const char* who = "pnmol_state_predict_marginals";
+    if (!f || !in || in->f != f || nq < 1 || !dt_q || (!means_qnd && !stds_qnd) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = std::string(who) + ": bad argument (null, foreign state, nq < 1, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    std::vector<DenseQuery> table((size_t)nq);
+    double sin[MAXN];
+    for (int a = 0; a < f->n; ++a) sin[a] = in->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, in->frame_dt);
+    for (int q = 0; q < nq; ++q) {
+        const double dt = dt_q[q];
+        if (!std::isfinite(dt) || dt < 0.0) {
+            ctx->err = std::string(who) + ": dt_q[" + std::to_string(q) + "] = " + std::to_string(dt) + " is negative or not finite";
+            return -1;
+        }
+        DenseQuery& e = table[(size_t)q];
+        std::memset(&e, 0, sizeof(e));
+        if (dt == 0.0) {  // the state itself
+            e.knot = 1;
+            for (int a = 0; a < f->n; ++a) e.sc[a] = sin[a];
+            continue;
+        }
+        // frame of dt: x_t ~ N(A1 (ts o m), A1 (ts ts^T o P) A1^T + Q1 (x) K), ts = frame change of the input
+        for (int a = 0; a < f->n; ++a) {
+            e.sc[a] = nordsieck_scale(f->nu, a, dt);
+            e.qbd[a] = f->iwp.Q1[a * MAXN + a];
+            for (int b2 = 0; b2 < f->n; ++b2) e.Bm[a * MAXN + b2] = f->iwp.A1[a * MAXN + b2] * (sin[b2] / nordsieck_scale(f->nu, b2, dt));
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t no = (size_t)nq * f->n * f->d, nb = pnmol_dense_block_doubles(f->n, f->dp);
+    int rc = ensure_dense_scratch(f, (nb + 2 * no) * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
+    if (rc != 0) return rc;
+    double* blk = static_cast<double*>(f->dn_scratch);
+    DenseFrames fr{};
+    for (int a = 0; a < f->n; ++a) fr.sl[a] = fr.sr[a] = 1.0;  // (the block stays in the state's frame; Bm carries the change)
+    if (pnmol_dense_launch_gather(ctx->stream, f->n, in->P, nullptr, nullptr, in->mean, nullptr, f->Kg, fr, f->dp, blk) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return -2;
+    }
+    return run_dense_eval(f, blk, true, table, 1, means_qnd, stds_qnd, who);
+}
+
+int pnmol_bridge_state(const pnmol_bridge* b, const pnmol_state* smooth_k, const pnmol_state* smooth_next, double t,
+                       pnmol_state* out) {
+    static const char* who = "pnmol_bridge_state";
+    if (!b || !smooth_k || !smooth_next || !out || out == smooth_k || out == smooth_next || smooth_k->f != b->f ||
+        smooth_next->f != b->f || out->f != b->f) {
+        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, aliasing, state of another filter)";
+        return -1;
+    }
+    pnmol_filter* f = b->f;
+    pnmol_ctx* ctx = f->ctx;
+    if (!b->Cfull) {
+        ctx->err = std::string(who) + ": this bridge was made without keep_full (no cross-covariance C_k)";
+        return -1;
+    }
+    if (!times_agree(smooth_k->t, b->t, b->dt) || !times_agree(smooth_next->t, b->t + b->dt, b->dt)) {
+        ctx->err = std::string(who) + ": the states sit at t = " + std::to_string(smooth_k->t) + " and " +
+                   std::to_string(smooth_next->t) + ", not at the two ends of the bridge's interval";
+        return -1;
+    }
+    const double th = (t - b->t) / b->dt;
+    if (!std::isfinite(t) || !(th > 0.0) || !(th < 1.0)) {
+        ctx->err = std::string(who) + ": t = " + std::to_string(t) + " is not strictly inside the bridge's interval (at its ends "
+                   "the posterior is the state given)";
+        return -1;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DenseMix c{};
+    bridge_coefficients(f, th, c.Bm, c.Bp, c.Qb);
+    for (int a = 0; a < f->n; ++a)
+        for (int e = 0; e < f->n; ++e) {
+            const double sh = nordsieck_scale(f->nu, e, b->dt);
+            c.BmS[a * MAXN + e] = c.Bm[a * MAXN + e] * ((smooth_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, e, smooth_k->frame_dt)) / sh);
+            c.BpS[a * MAXN + e] = c.Bp[a * MAXN + e] * ((smooth_next->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, e, smooth_next->frame_dt)) / sh);
+        }
+    const double* ml = b->blk + 3 * (size_t)f->n * f->n * f->dp;
+    if (pnmol_dense_launch_state(ctx->stream, f->n, smooth_k->P, smooth_next->P, b->Cfull, f->Kg, ml, ml + (size_t)f->n * f->dp, c,
+                                 f->dp, out->P, out->var, out->mean) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return -2;
+    }
+    out->t = t;
+    out->frame_dt = b->dt;
     return 0;
 }
 
@@ -5250,6 +5643,83 @@ int pnmol_samples_step_back(pnmol_samples* x, const pnmol_state* filt_k, double 
     x->drawn = false;
     if ((rc = finish_sampler_call(f, true, who)) != 0) return rc;
     x->t = filt_k->t, x->frame_dt = dt, x->drawn = true;
+    return 0;
+}
+
+int pnmol_samples_clone(const pnmol_samples* x, pnmol_samples** out) {
+    if (out) *out = nullptr;
+    if (!x || !out) return -1;
+    int rc = pnmol_samples_create(x->f, x->S, out);
+    if (rc != 0) return rc;
+    pnmol_ctx* ctx = x->f->ctx;
+    pnmol_samples* o = *out;
+    HIPCHK(ctx, hipMemcpyAsync(o->X, x->X, sizeof(double) * (size_t)x->f->Dp * x->Sp, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    o->t = x->t, o->frame_dt = x->frame_dt, o->drawn = x->drawn;
+    return 0;
+}
+
+int pnmol_samples_interpolate(pnmol_samples* out, const pnmol_samples* left, const pnmol_samples* right, double t,
+                              const double* xi_SD, unsigned long long seed, unsigned long long step_index, double scale) {
+    static const char* who = "pnmol_samples_interpolate";
+    if (!out || !left || out == left || out == right || left->f != out->f || (right && right->f != out->f) || left->S != out->S ||
+        (right && right->S != out->S) || !left->drawn || (right && !right->drawn) || !std::isfinite(scale) || !std::isfinite(t) ||
+        !(t > left->t) || (right && !(t < right->t))) {
+        if (out)
+            out->f->ctx->err = std::string(who) + ": bad argument (null, aliasing blocks, blocks of another filter or size, a block "
+                                                  "that holds no draw, non-finite scale, or t not strictly between the blocks' times)";
+        return -1;
+    }
+    pnmol_filter* f = out->f;
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = ensure_sampler_ws(f, who);
+    if (rc != 0) return rc;
+    // frame of h = t_r - t_l (two-sided) or of h = t - t_l (one-sided: the prior carried forwards, B+ = 0, Qb = Q1)
+    const double h = (right ? right->t : t) - left->t;
+    DenseDrawMix c{};
+    double Bm[MAXN * MAXN] = {0}, Bp[MAXN * MAXN] = {0}, Qb[MAXN * MAXN] = {0};
+    if (right) {
+        bridge_coefficients(f, (t - left->t) / h, Bm, Bp, Qb);
+    } else {
+        std::memcpy(Bm, f->iwp.A1, sizeof(Bm));
+        std::memcpy(Qb, f->iwp.Q1, sizeof(Qb));
+    }
+    for (int a = 0; a < f->n; ++a) {  // chol(Qb), positive semi-definite: a pivot that is not positive gives a zero column
+        for (int b = 0; b <= a; ++b) {
+            double v = Qb[a * MAXN + b];
+            for (int e = 0; e < b; ++e) v -= c.Ls[a * MAXN + e] * c.Ls[b * MAXN + e];
+            if (a == b) c.Ls[a * MAXN + a] = v > 0.0 ? std::sqrt(v) : 0.0;
+            else c.Ls[a * MAXN + b] = c.Ls[b * MAXN + b] > 0.0 ? v / c.Ls[b * MAXN + b] : 0.0;
+        }
+    }
+    for (int a = 0; a < f->n; ++a)
+        for (int b = 0; b < f->n; ++b) {
+            const double sh = nordsieck_scale(f->nu, b, h);
+            c.BmS[a * MAXN + b] = Bm[a * MAXN + b] * ((left->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, b, left->frame_dt)) / sh);
+            if (right) c.BpS[a * MAXN + b] = Bp[a * MAXN + b] * ((right->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, b, right->frame_dt)) / sh);
+            c.Ls[a * MAXN + b] *= scale;
+        }
+    out->drawn = false;
+    const long Dp = f->Dp;
+    const int Sp = out->Sp, D = f->n * f->d;
+    double* Xi2 = out->Xi + Dp * Sp;  // derivative-major noise rows (the xi_2 half of the block's noise buffer)
+    if (xi_SD) {
+        HIPCHK(ctx, hipMemcpyAsync(out->stage, xi_SD, sizeof(double) * (size_t)out->S * D, hipMemcpyHostToDevice, st));
+        rc = pnmol_sample_launch_scatter(st, out->stage, out->S, D, f->d, f->dp, 0, Sp, Xi2);
+    } else {
+        rc = pnmol_sample_launch_noise(st, seed, step_index, out->S, D, f->d, f->dp, 0, Sp, Xi2, nullptr);
+    }
+    if (rc == 0) rc = pnmol_sample_launch_thin(st, f->sp_Gamma, Xi2, out->R, nullptr, nullptr, 1.0, f->dp, Sp, 0, 1, f->n, 0);
+    if (rc == 0) rc = pnmol_dense_launch_draw_mix(st, f->n, c, f->dp, Sp, left->X, right ? right->X : nullptr, out->R, out->X);
+    if (rc != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    out->t = t, out->frame_dt = h, out->drawn = true;
     return 0;
 }
 

@@ -75,11 +75,21 @@ SYMBOLS = {
     "pnmol_state_get_marginal_var": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_filter_step": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp, ctypes.POINTER(StepOut), _c_double_p]),
     "pnmol_smoother_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
+    "pnmol_state_predict": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp]),
+    "pnmol_state_predict_marginals": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p]),
+    "pnmol_smoother_step_bridge": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "pnmol_bridge_destroy": (ctypes.c_int, [_vp]),
+    "pnmol_bridge_get_interval": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_bridge_eval": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p]),
+    "pnmol_bridge_state": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "pnmol_samples_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp)]),
     "pnmol_samples_destroy": (ctypes.c_int, [_vp]),
     "pnmol_samples_draw": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_double]),
     "pnmol_samples_step_back": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _c_double_p, ctypes.c_ulonglong, ctypes.c_ulonglong,
                                                ctypes.c_double]),
+    "pnmol_samples_interpolate": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _c_double_p, ctypes.c_ulonglong,
+                                                 ctypes.c_ulonglong, ctypes.c_double]),
+    "pnmol_samples_clone": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_samples_get": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_samples_get_time": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_sample_noise": (ctypes.c_int, [_vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
@@ -287,6 +297,7 @@ class Filter:
         # exactly when a filter and its states die together -- and the states' device buffers would leak.
         self._live = {}
         self._live_samples = {}     # the same for the pnmol_samples objects (Samples)
+        self._live_bridges = {}     # ... and the pnmol_bridge objects (Bridge)
 
     def __del__(self):
         # The cyclic garbage collector (and interpreter shutdown) finalises a filter and its states in ANY order: the
@@ -299,6 +310,10 @@ class Filter:
         while live:
             _, sh = live.popitem()
             self.lib.pnmol_samples_destroy(sh)
+        live = getattr(self, "_live_bridges", None)
+        while live:
+            _, sh = live.popitem()
+            self.lib.pnmol_bridge_destroy(sh)
         h, self.handle = getattr(self, "handle", None), None
         if h:
             self.lib.pnmol_filter_destroy(h)
@@ -362,12 +377,41 @@ class Filter:
         self.ctx.check(rc, "pnmol_filter_step")
         return out, info, err
 
-    def smoother_step(self, filt_k, smooth_next, dt):
-        """One RTS backward step on the device (`pnmol_smoother_step`): a new State, the smoothed state at filt_k.t."""
+    def smoother_step(self, filt_k, smooth_next, dt, bridge=None):
+        """One RTS backward step on the device (`pnmol_smoother_step`): a new State, the smoothed state at filt_k.t.
+        bridge="marginal" / "full": `pnmol_smoother_step_bridge` instead, returning (State, Bridge): the same state bit for
+        bit and what dense output inside [filt_k.t, filt_k.t + dt] needs ("full": with the cross-covariance C_k, Dp^2 doubles)."""
         out = State(self)
-        rc = self.lib.pnmol_smoother_step(self.handle, filt_k.handle, smooth_next.handle, float(dt), out.handle)
-        self.ctx.check(rc, "pnmol_smoother_step")
+        if bridge is None:
+            rc = self.lib.pnmol_smoother_step(self.handle, filt_k.handle, smooth_next.handle, float(dt), out.handle)
+            self.ctx.check(rc, "pnmol_smoother_step")
+            return out
+        if bridge not in ("marginal", "full"):
+            raise ValueError(f'bridge must be None, "marginal" or "full", got {bridge!r}')
+        h = _vp()
+        rc = self.lib.pnmol_smoother_step_bridge(self.handle, filt_k.handle, smooth_next.handle, float(dt), out.handle,
+                                                 int(bridge == "full"), ctypes.byref(h))
+        self.ctx.check(rc, "pnmol_smoother_step_bridge")
+        t = ctypes.c_double(0.0)
+        self.lib.pnmol_state_get_time(out.handle, ctypes.byref(t))
+        return out, Bridge(self, h, (t.value, float(dt), bridge == "full"))
+
+    def predict(self, state, dt):
+        """The prior alone carried over dt > 0 from `state` (`pnmol_state_predict`): a new State at state.t + dt."""
+        out = State(self)
+        self.ctx.check(self.lib.pnmol_state_predict(self.handle, state.handle, float(dt), out.handle), "pnmol_state_predict")
         return out
+
+    def predict_marginals(self, state, dts):
+        """(means, stds), each (len(dts), n, d): the prediction from `state` over every dts[i] >= 0, all derivatives, raw
+        coordinates (`pnmol_state_predict_marginals`)."""
+        dts = _f64(np.atleast_1d(dts))
+        if dts.ndim != 1 or dts.size < 1:
+            raise ValueError(f"expected a non-empty 1-d array of step sizes, got shape {dts.shape}")
+        means, stds = np.empty((dts.size, self.n, self.d)), np.empty((dts.size, self.n, self.d))
+        rc = self.lib.pnmol_state_predict_marginals(self.handle, state.handle, dts.size, _dp(dts), _dp(means), _dp(stds))
+        self.ctx.check(rc, "pnmol_state_predict_marginals")
+        return means, stds
 
     def steps(self, state, k, dt, want_means=True, want_stds=True):
         means = np.empty((k, self.d)) if want_means else None
@@ -481,15 +525,60 @@ class State:
         return out
 
 
+class Bridge:
+    """`pnmol_bridge`: what dense output inside one step [t, t + dt] of a smoothed solution needs, device-resident."""
+
+    def __init__(self, flt, handle, interval=None):
+        self.filter, self.lib, self.ctx = flt, flt.lib, flt.ctx
+        self.handle = handle
+        flt._live_bridges[id(self)] = handle
+        if interval is None:                            # (t, dt, full) as the maker of the bridge knows them, or from the library
+            t, dt, full = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+            self.lib.pnmol_bridge_get_interval(handle, ctypes.byref(t), ctypes.byref(dt), ctypes.byref(full))
+            interval = (t.value, dt.value, bool(full.value))
+        self.t, self.dt, self.full = interval
+
+    def _destroy(self):
+        h, self.handle = getattr(self, "handle", None), None
+        flt = getattr(self, "filter", None)
+        # (no entry: Filter.__del__ ran first and has destroyed this bridge's handle already)
+        if h and flt is not None and flt._live_bridges.pop(id(self), None) is not None:
+            self.lib.pnmol_bridge_destroy(h)
+
+    def __del__(self):
+        self._destroy()
+
+    def eval(self, ts):
+        """(means, stds), each (len(ts), n, d): posterior mean and marginal std of all derivatives at the times `ts` inside
+        [t, t + dt], raw coordinates (`pnmol_bridge_eval`: one launch, the read-out copied into the result arrays)."""
+        ts = _f64(np.atleast_1d(ts))
+        if ts.ndim != 1 or ts.size < 1:
+            raise ValueError(f"expected a non-empty 1-d array of times, got shape {ts.shape}")
+        f = self.filter
+        means, stds = np.empty((ts.size, f.n, f.d)), np.empty((ts.size, f.n, f.d))
+        self.ctx.check(self.lib.pnmol_bridge_eval(self.handle, ts.size, _dp(ts), _dp(means), _dp(stds)), "pnmol_bridge_eval")
+        return means, stds
+
+    def state(self, smooth_k, smooth_next, t):
+        """The full posterior at t strictly inside the interval as a new State (`pnmol_bridge_state`; needs a "full" bridge);
+        smooth_k / smooth_next: the smoothed states at the two ends."""
+        out = State(self.filter)
+        rc = self.lib.pnmol_bridge_state(self.handle, smooth_k.handle, smooth_next.handle, float(t), out.handle)
+        self.ctx.check(rc, "pnmol_bridge_state")
+        return out
+
+
 class Samples:
     """`pnmol_samples`: S joint draws of the state at one time point, device-resident; `draw` at the terminal state, then
     `step_back` through the filtered states in decreasing time."""
 
-    def __init__(self, flt, num_samples):
+    def __init__(self, flt, num_samples, _handle=None):
         self.filter, self.lib, self.ctx = flt, flt.lib, flt.ctx
         self.num_samples = int(num_samples)
-        h = _vp()
-        self.ctx.check(self.lib.pnmol_samples_create(flt.handle, self.num_samples, ctypes.byref(h)), "pnmol_samples_create")
+        h = _handle
+        if h is None:
+            h = _vp()
+            self.ctx.check(self.lib.pnmol_samples_create(flt.handle, self.num_samples, ctypes.byref(h)), "pnmol_samples_create")
         self.handle = h
         flt._live_samples[id(self)] = h
 
@@ -519,6 +608,20 @@ class Samples:
         rc = self.lib.pnmol_samples_step_back(self.handle, filt_k.handle, float(dt), None if a is None else _dp(a), int(seed),
                                               int(step_index), float(scale))
         self.ctx.check(rc, "pnmol_samples_step_back")
+
+    def clone(self):
+        """A copy of this block (`pnmol_samples_clone`)."""
+        h = _vp()
+        self.ctx.check(self.lib.pnmol_samples_clone(self.handle, ctypes.byref(h)), "pnmol_samples_clone")
+        return Samples(self.filter, self.num_samples, h)
+
+    def interpolate(self, left, right, t, xi=None, *, seed=0, step_index=0, scale=1.0):
+        """This block <- draws at t, left.t < t < right.t, coupled to the draws in `left` and `right` (`pnmol_samples_interpolate`);
+        right=None carries `left` forwards by the prior.  xi (S, D) or None (device generator)."""
+        a = self._noise(xi, self.filter.n * self.filter.d)
+        rc = self.lib.pnmol_samples_interpolate(self.handle, left.handle, None if right is None else right.handle, float(t),
+                                                None if a is None else _dp(a), int(seed), int(step_index), float(scale))
+        self.ctx.check(rc, "pnmol_samples_interpolate")
 
     def get(self):
         """The draws as (S, n, d), raw coordinates."""

@@ -12,6 +12,42 @@ import scipy.linalg
 import scipy.special
 
 
+def _partial_interval(theta, num_derivatives):
+    """(A_th, Q_th): transition and process noise of the IWP over the fraction theta of a step, in the Nordsieck frame of
+    the WHOLE step.  A_th[a, b] = A1[a, b] th^(b - a), Q_th[a, b] = Q1[a, b] th^(2 nu + 1 - a - b), entry by entry: every
+    exponent that meets a non-zero entry is >= 0 (A1 is upper triangular), so nothing is divided by a power of theta."""
+    n = num_derivatives + 1
+    A1 = np.flip(scipy.linalg.pascal(n, kind="lower", exact=False))
+    Q1 = np.flip(scipy.linalg.hilbert(n))
+    a = np.arange(n)
+    A = np.triu(A1) * theta ** np.maximum(a[None, :] - a[:, None], 0)
+    Q = Q1 * theta ** (2 * num_derivatives + 1 - a[:, None] - a[None, :])
+    return A, Q
+
+
+def bridge_coefficients(theta, num_derivatives):
+    """(B_minus, B_plus, Qb), each (n, n): the IWP prior's bridge over one step, in the Nordsieck frame of that step.
+
+    With x_l, x_r the states at the two ends of a step h and t = t_l + theta h, 0 < theta < 1,
+        x_t | x_l, x_r ~ N((B_minus (x) I) x_l + (B_plus (x) I) x_r, Qb (x) K).
+    There is no measurement inside a step, so the same law holds under the filtering / smoothing posterior: it is what
+    dense output and draws between grid times are built from.  By Chapman-Kolmogorov,
+    A_(1-th) Q_th A_(1-th)^T + Q_(1-th) = Q1, the gain of conditioning x_t on x_r is B_plus = Q_th A_(1-th)^T Q1^-1; then
+    B_minus = (I - B_plus A_(1-th)) A_th and Qb in Joseph form (symmetric positive semi-definite by construction)."""
+    theta = float(theta)
+    if not 0.0 < theta < 1.0:
+        raise ValueError(f"bridge_coefficients: theta must lie strictly inside (0, 1), got {theta}")
+    n = num_derivatives + 1
+    Q1 = np.flip(scipy.linalg.hilbert(n))
+    A_th, Q_th = _partial_interval(theta, num_derivatives)
+    A_c, Q_c = _partial_interval(1.0 - theta, num_derivatives)
+    B_plus = scipy.linalg.cho_solve(scipy.linalg.cho_factor(Q1, lower=True), A_c @ Q_th).T
+    M = np.eye(n) - B_plus @ A_c
+    B_minus = M @ A_th
+    Qb = M @ Q_th @ M.T + B_plus @ Q_c @ B_plus.T
+    return B_minus, B_plus, 0.5 * (Qb + Qb.T)
+
+
 class IntegratedWienerTransition(namedtuple("_IWP", "wiener_process_dimension num_derivatives wp_diffusion_sqrtm")):
     @cached_property
     def preconditioned_discretize_1d(self):

@@ -21,15 +21,91 @@ class PDEFilterState(namedtuple("_", "t y error_estimate reference_state diffusi
     """PDE filter state (pdefilter.py:17-22)."""
 
 
+class DenseOutput(namedtuple("_DenseOutput", "t mean marginal_std")):
+    """Posterior between (or at) grid times: t (Tq,), mean (Tq, n, d), marginal_std (Tq, n, d), uncalibrated."""
+
+
 class PDESolution:
     """t (T+1,), mean (T+1,n,d), cov_sqrtm (T+1,D,D) [lazy], info, diffusion_squared_calibrated
-    (pdefilter.py:25-31)."""
+    (pdefilter.py:25-31).
 
-    def __init__(self, t, mean, ys, info, diffusion_squared_calibrated):
+    Beyond the reference: `solution(t)` and `solution.state_at(t)` evaluate the posterior at ANY t >= t[0] (dense output,
+    DESIGN.md section 14).  A filtering solution answers by prediction from the grid state on the left; a smoothed one
+    (`solver.smooth`) from the bridges it keeps per step (`bridges`: a list of T `pnmol._hip.Bridge`, or None), and beyond the
+    last grid time by prediction as well."""
+
+    def __init__(self, t, mean, ys, info, diffusion_squared_calibrated, bridges=None, smoothed=False):
         self.t, self.mean, self.info = t, mean, info
         self.diffusion_squared_calibrated = diffusion_squared_calibrated
         self._ys = ys
         self._cov_sqrtm = None
+        self.bridges = bridges
+        self.smoothed = smoothed
+
+    def _dense_setup(self, t, what):
+        from .base import rv
+
+        ts = np.atleast_1d(np.asarray(t, dtype=np.float64))
+        if ts.ndim != 1 or ts.size < 1:
+            raise ValueError(f"{what}: expected a time or a non-empty 1-d array of times, got shape {np.shape(t)}")
+        grid = np.asarray(self.t, dtype=np.float64)
+        if not np.all(np.isfinite(ts)) or np.any(ts < grid[0]):
+            raise ValueError(f"{what}: times must be finite and >= t[0] = {grid[0]} (the posterior is not defined before the "
+                             f"initial time)")
+        if not self._ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in self._ys):
+            raise TypeError(f"{what} needs the device-resident states of this package's solve() / smooth()")
+        k = np.searchsorted(grid, ts, side="right") - 1
+        inside = k < len(grid) - 1
+        if self.smoothed and self.bridges is None and np.any(inside & (grid[k] != ts)):
+            raise RuntimeError(f'{what}: this smoothed solution keeps no bridges (it was made with dense=None); call '
+                               f'solver.smooth(solution, dense="marginal") (or dense="full" for state_at)')
+        return ts, grid, k
+
+    def __call__(self, t):
+        """Posterior mean and marginal std of all derivatives at the time(s) t >= self.t[0]: a `DenseOutput` with t (Tq,),
+        mean (Tq, n, d), marginal_std (Tq, n, d), uncalibrated like `marginal_std`.  Queries may come in any order; they are
+        grouped per grid interval and answered by one device call per touched interval.  A grid time returns the stored
+        values."""
+        ts, grid, k = self._dense_setup(t, "PDESolution.__call__")
+        flt = self._ys[0].device_state.filter
+        mean, std = np.empty((ts.size, flt.n, flt.d)), np.empty((ts.size, flt.n, flt.d))
+        on_grid = grid[k] == ts
+        for i in np.unique(k):
+            sel = np.flatnonzero(k == i)
+            stored = sel[on_grid[sel]]
+            if stored.size:
+                mean[stored] = self.mean[i]
+                std[stored] = np.sqrt(np.maximum(self._ys[i].marginal_var, 0.0))
+            sel = sel[~on_grid[sel]]
+            if not sel.size:
+                continue
+            if self.smoothed and i < len(grid) - 1:
+                mean[sel], std[sel] = self.bridges[i].eval(ts[sel])
+            else:
+                mean[sel], std[sel] = flt.predict_marginals(self._ys[i].device_state, ts[sel] - grid[i])
+        return DenseOutput(t=ts, mean=mean, marginal_std=std)
+
+    def state_at(self, t):
+        """The full posterior at one time t >= self.t[0] as a `DeviceMultivariateNormal` (mean, `cov`, `cov_sqrtm`,
+        `marginal_var`).  Inside a smoothed solution this needs `smooth(solution, dense="full")`; a filtering solution, and any
+        t beyond the last grid time, is answered by prediction.  A grid time returns the stored state."""
+        from .base import rv
+
+        if np.ndim(t) != 0:
+            raise ValueError("PDESolution.state_at: expected a single time")
+        ts, grid, k = self._dense_setup(t, "PDESolution.state_at")
+        i, tq = int(k[0]), float(ts[0])
+        if grid[i] == tq:
+            return self._ys[i]
+        flt = self._ys[0].device_state.filter
+        if self.smoothed and i < len(grid) - 1:
+            if not self.bridges[i].full:
+                raise RuntimeError('PDESolution.state_at: the full covariance between grid times needs the cross-covariances '
+                                   'of the smoother; call solver.smooth(solution, dense="full")')
+            dev = self.bridges[i].state(self._ys[i].device_state, self._ys[i + 1].device_state, tq)
+        else:
+            dev = flt.predict(self._ys[i].device_state, tq - grid[i])
+        return rv.DeviceMultivariateNormal(dev.mean(), dev)
 
     @property
     def cov_sqrtm(self):

@@ -303,7 +303,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
 
     # ------------------------------------------------------------------ smoothing
-    def smooth(self, solution):
+    def smooth(self, solution, dense="marginal"):
         """Rauch-Tung-Striebel smoothing of a `solve()` result (kalman.py:33-46 of the reference, covariance form).
 
         Walks `solution`'s device-resident states backwards, one `pnmol_smoother_step` per step, with the filter that owns
@@ -311,9 +311,15 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         linearisation of a semilinear solver enters only through the filtered states).  Returns a `PDESolution` with the
         same `t`, `info` and `diffusion_squared_calibrated`, the smoothed `mean` and device-resident states, so
         `marginal_std` and `cov_sqrtm` work as for the filter -- and, like them, uncalibrated.  `solution` is unchanged.
+        dense: what the result keeps for evaluation BETWEEN grid times (`result(t)`, `result.state_at(t)`).
+        "marginal" (default): one bridge per step, ~3 n^2 d doubles and one tiny launch each -- means and marginal stds at any t;
+        the smoothed states are bit for bit those of dense=None.  "full": the bridges also keep the lag-one cross-covariance
+        C_k, T (n d)^2 more doubles on the device in all (as much as the states themselves), for `state_at`.  None: nothing.
         Supported: fp64 white-noise solvers (pnmol.white), constant and adaptive steps."""
         from . import latent, sqrtform
 
+        if dense not in (None, "marginal", "full"):
+            raise ValueError(f'smooth(): dense must be None, "marginal" or "full", got {dense!r}')
         if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
             raise TypeError(f"smooth() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
@@ -326,12 +332,20 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         t = np.asarray(solution.t)
         nxt = ys[-1].device_state.clone()                       # terminal state: the filtered one
         out = [rv.DeviceMultivariateNormal(np.array(ys[-1].mean), nxt)]
+        bridges = None if dense is None else []
         for k in range(len(ys) - 2, -1, -1):
-            nxt = flt.smoother_step(ys[k].device_state, nxt, t[k + 1] - t[k])
+            if dense is None:
+                nxt = flt.smoother_step(ys[k].device_state, nxt, t[k + 1] - t[k])
+            else:
+                nxt, br = flt.smoother_step(ys[k].device_state, nxt, t[k + 1] - t[k], bridge=dense)
+                bridges.append(br)
             out.append(rv.DeviceMultivariateNormal(nxt.mean(), nxt))
         out.reverse()
+        if bridges is not None:
+            bridges.reverse()
         return pdefilter.PDESolution(t=solution.t, mean=np.stack([y.mean for y in out]), ys=out, info=solution.info,
-                                     diffusion_squared_calibrated=solution.diffusion_squared_calibrated)
+                                     diffusion_squared_calibrated=solution.diffusion_squared_calibrated, bridges=bridges,
+                                     smoothed=True)
 
     # ------------------------------------------------------------------ joint draws
     def sample(self, solution, num_samples, *, seed=0, noise=None, calibrated=False):
@@ -352,28 +366,89 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
             raise TypeError(f"sample() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+        return self._sample_walk("sample", solution, num_samples, seed, noise, calibrated)[0]
+
+    def sample_dense(self, solution, num_samples, ts, *, seed=0, noise=None, noise_dense=None, calibrated=False):
+        """Joint draws of whole trajectories at the grid times AND at the times `ts` (1-d, any order, >= solution.t[0]).
+
+        Returns (grid_draws (S, T+1, n, d), dense_draws (S, len(ts), n, d)), raw coordinates.  `grid_draws` is bit for bit
+        `sample(solution, num_samples, seed=seed, noise=noise, calibrated=calibrated)`.  Given the draws at the two grid times
+        around it, a time inside a step follows the prior's bridge (no measurement in between), so it is drawn by
+        `pnmol_samples_interpolate` from the two neighbouring blocks alone; several times inside one step are drawn one after the
+        other, each between its nearest drawn neighbours, and times beyond the last grid time forwards, each from its
+        predecessor.  A time equal to a grid time returns that grid time's draws.  The inserted time `ts[q]` uses
+        `step_index = T + 1 + q` of the device generator, or `noise_dense[q]` (S, D) when host noise is given (`noise` and
+        `noise_dense` together, or neither).  `solution` (a `solve()` result, as for `sample`) is unchanged."""
+        ts = np.atleast_1d(np.asarray(ts, dtype=np.float64))
+        if ts.ndim != 1:
+            raise ValueError(f"sample_dense(): ts must be 1-d, got shape {ts.shape}")
+        if ts.size and (not np.all(np.isfinite(ts)) or np.any(ts < np.asarray(solution.t)[0])):
+            raise ValueError("sample_dense(): times must be finite and >= solution.t[0]")
+        if (noise is None) != (noise_dense is None):
+            raise ValueError("sample_dense(): give noise and noise_dense together (host noise for every input) or neither")
+        if noise_dense is not None and len(noise_dense) != ts.size:
+            raise ValueError(f"sample_dense(): noise_dense must have one entry per time in ts ({ts.size}), got {len(noise_dense)}")
+        return self._sample_walk("sample_dense", solution, num_samples, seed, noise, calibrated, ts, noise_dense)
+
+    def _sample_walk(self, who, solution, num_samples, seed, noise, calibrated, ts=None, noise_dense=None):
+        from . import latent, sqrtform
+
+        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
+            raise TypeError(f"{who}() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
         ys = list(solution._ys)
         if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
-            raise TypeError("sample() needs the device-resident states of this package's solve()")
+            raise TypeError(f"{who}() needs the device-resident states of this package's solve()")
         flt = ys[-1].device_state.filter
         if any(y.device_state.filter is not flt for y in ys):
-            raise ValueError("sample(): the states of the solution belong to different device filters")
+            raise ValueError(f"{who}(): the states of the solution belong to different device filters")
         S, T = int(num_samples), len(ys) - 1
         if S < 1:
-            raise ValueError(f"sample(): num_samples must be at least 1, got {num_samples}")
+            raise ValueError(f"{who}(): num_samples must be at least 1, got {num_samples}")
         if noise is not None and len(noise) != T + 1:
-            raise ValueError(f"sample(): noise must have one entry per time point ({T + 1}), got {len(noise)}")
+            raise ValueError(f"{who}(): noise must have one entry per time point ({T + 1}), got {len(noise)}")
         scale = float(np.sqrt(solution.diffusion_squared_calibrated)) if calibrated else 1.0
         t = np.asarray(solution.t)
         xi = (lambda k: None) if noise is None else (lambda k: noise[k])
         block = flt.new_samples(S)
         out = np.empty((S, T + 1, flt.n, flt.d))
+        # the inserted times, per grid interval (index T: beyond the last grid time), ascending inside each
+        nq = 0 if ts is None else ts.size
+        dense = np.empty((S, nq, flt.n, flt.d))
+        where = np.searchsorted(t, ts, side="right") - 1 if nq else np.zeros(0, dtype=int)
+        on_grid = t[where] == ts if nq else np.zeros(0, dtype=bool)
+        todo = {}
+        for q in np.argsort(ts, kind="stable") if nq else ():
+            if not on_grid[q]:
+                todo.setdefault(int(where[q]), []).append(int(q))
+        spare = [flt.new_samples(S), flt.new_samples(S)] if todo else None
+
+        def insert(k, left, right):
+            drawn = 0                                           # blocks alternate by the draws made: `left` is never `cur`
+            for i, q in enumerate(todo[k]):
+                if i and ts[q] == ts[todo[k][i - 1]]:           # the same time twice: the same draws
+                    dense[:, q] = dense[:, todo[k][i - 1]]
+                    continue
+                cur = spare[drawn % 2]
+                drawn += 1
+                cur.interpolate(left, right, ts[q], None if noise_dense is None else noise_dense[q], seed=seed,
+                                step_index=T + 1 + q, scale=scale)
+                dense[:, q] = cur.get()
+                left = cur
+
         block.draw(ys[-1].device_state, xi(T), seed=seed, step_index=T, scale=scale)
         out[:, T] = block.get()
+        if T in todo:
+            insert(T, block, None)
         for k in range(T - 1, -1, -1):
+            right = block.clone() if k in todo else None        # (step_back works in place)
             block.step_back(ys[k].device_state, t[k + 1] - t[k], xi(k), seed=seed, step_index=k, scale=scale)
             out[:, k] = block.get()
-        return out
+            if k in todo:
+                insert(k, block, right)
+        for q in np.flatnonzero(on_grid):
+            dense[:, q] = out[:, where[q]]
+        return out, dense
 
 
 class LinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
