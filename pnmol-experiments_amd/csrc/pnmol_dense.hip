@@ -1,5 +1,5 @@
-// pnmol_dense.hip -- kernels of the dense output between grid times (`pnmol_bridge_*`, `pnmol_state_predict*`,
-// include/pnmol_hip.h).
+// pnmol_dense.hip -- the dense output between grid times (`pnmol_bridge_*`, `pnmol_state_predict*`, include/pnmol_hip.h;
+// DESIGN.md section 14): kernels, then host side.
 //
 // Between two grid times there is no measurement, so the posterior at t given the two neighbouring states is the bridge of the
 // prior IWP (x) K, whose gains are n x n matrices Kronecker the identity (pnmol/base/iwp.py, bridge_coefficients):
@@ -9,6 +9,8 @@
 // mesh points and memory-bound; no MFMA.  Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp,
 // row-major, zero padding (dp is a multiple of 32).
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "pnmol_internal.hpp"
 
@@ -302,8 +304,6 @@ __global__ __launch_bounds__(256) void k_dn_draw_mix(DenseDrawMix c, int dp, int
     }
 }
 
-}  // namespace
-
 #define DN_SWITCH(n, CALL)          \
     switch (n) {                    \
         case 2: { constexpr int N = 2; CALL; } break; \
@@ -312,14 +312,17 @@ __global__ __launch_bounds__(256) void k_dn_draw_mix(DenseDrawMix c, int dp, int
         default: return -1;         \
     }
 
-int pnmol_dense_launch_gather(hipStream_t st, int n, const double* Pl, const double* Cx, const double* Pr, const double* ml,
+// blk <- point-diagonal blocks of sl sl^T o Pl, Cx (as it is), sr sr^T o Pr, sl o ml, sr o mr, diag K (Cx / Pr / mr may be null:
+// the one-sided case, their part of blk is left alone)
+int launch_gather(hipStream_t st, int n, const double* Pl, const double* Cx, const double* Pr, const double* ml,
                               const double* mr, const double* Kg, const DenseFrames& c, int dp, double* blk) {
     const unsigned g = (unsigned)((dp + 255) / 256);
     DN_SWITCH(n, (k_dn_gather<N><<<g, 256, 0, st>>>(Pl, Cx, Pr, ml, mr, Kg, c, dp, blk)));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int pnmol_dense_launch_eval(hipStream_t st, int n, int d, int dp, int nq, const double* blk, const DenseQuery* table, int one_sided,
+// means / stds (nq, n, d) row-major on the device from blk and the table of nq rows; one_sided: the Bp terms are skipped
+int launch_eval(hipStream_t st, int n, int d, int dp, int nq, const double* blk, const DenseQuery* table, int one_sided,
                             double* means, double* stds) {
     // (gridDim.y is limited to 65535)
     for (int q0 = 0; q0 < nq; q0 += 65535) {
@@ -331,7 +334,8 @@ int pnmol_dense_launch_eval(hipStream_t st, int n, int d, int dp, int nq, const 
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int pnmol_dense_launch_predict(hipStream_t st, int n, const double* P, const double* m, const double* Kg, const SmoothConsts& c,
+// Pout = A1 (ts ts^T o P) A1^T + Q1 (x) K, var = diag, mout = A1 (ts o m)   (c.ts: frame change of the input; c.tsn unused)
+int launch_predict(hipStream_t st, int n, const double* P, const double* m, const double* Kg, const SmoothConsts& c,
                                int dp, double* Pout, double* var, double* mout) {
     const dim3 grid(dp / 32, dp / 8), blk(32, 8);
     MeanMats mm{};
@@ -343,7 +347,8 @@ int pnmol_dense_launch_predict(hipStream_t st, int n, const double* P, const dou
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int pnmol_dense_launch_state(hipStream_t st, int n, const double* Pl, const double* Pr, const double* C, const double* Kg,
+// Pout = BmS Pl BmS^T + Bm C Bp^T + (Bm C Bp^T)^T + BpS Pr BpS^T + Qb (x) K (both halves, var = diag), mout = Bm ml + Bp mr
+int launch_state(hipStream_t st, int n, const double* Pl, const double* Pr, const double* C, const double* Kg,
                              const double* ml, const double* mr, const DenseMix& c, int dp, double* Pout, double* var, double* mout) {
     const dim3 grid(dp / 32, dp / 32);
     MeanMats mm{};
@@ -355,9 +360,341 @@ int pnmol_dense_launch_state(hipStream_t st, int n, const double* Pl, const doub
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+}  // namespace
+
 int pnmol_dense_launch_draw_mix(hipStream_t st, int n, const DenseDrawMix& c, int dp, int Sp, const double* xl, const double* xr,
                                 const double* W, double* out) {
     const unsigned grid = (unsigned)(((long)dp * Sp + 255) / 256);
     DN_SWITCH(n, (k_dn_draw_mix<N><<<grid, 256, 0, st>>>(c, dp, Sp, xl, xr, W, out)));
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+void pnmol_dense_free_ws(pnmol_filter* f) {
+    if (f->dn_scratch) (void)hipFree(f->dn_scratch);
+    if (f->dn_slab) {  // (no bridge is alive: the slab is empty)
+        if (f->dn_slab->base) (void)hipFree(f->dn_slab->base);
+        delete f->dn_slab;
+    }
+    f->dn_scratch = nullptr, f->dn_cap = 0, f->dn_slab = nullptr;
+}
+
+// Enqueued behind the smoother step, before the next one reuses its buffers: the point-diagonal blocks of Ps_k (out),
+// C_k = G Ps^h (sm_C) and Ps^h_{k+1} (the product k_sm_build formed), the two means, diag K; with keep_full all of C_k.
+int pnmol_dense_make_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                            const pnmol_state* out, const double* tsn, int keep_full, pnmol_bridge** bridge) {
+    static const char* who = "pnmol_smoother_step_bridge";
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t sq = (size_t)f->Dp * f->Dp;
+    pnmol_bridge* br = new pnmol_bridge();
+    br->f = f, br->t = filt_k->t, br->dt = dt;
+    f->bridges.fetch_add(1);
+    auto fail = [&](int code, const std::string& why) {
+        ctx->err = std::string(who) + ": " + why;
+        (void)hipStreamSynchronize(st);
+        pnmol_bridge_destroy(br);
+        return code;
+    };
+    const size_t slot = pnmol_dense_block_doubles(f->n, f->dp);
+    hipError_t e = hipSuccess;
+    if (!f->dn_slab || f->dn_slab->used == BRIDGE_SLAB_SLOTS) {  // (a full slab now belongs to its bridges alone)
+        BridgeSlab* sl = new BridgeSlab();
+        e = hipMalloc(&sl->base, sizeof(double) * slot * BRIDGE_SLAB_SLOTS);
+        if (e == hipSuccess) f->dn_slab = sl;
+        else delete sl;
+    }
+    if (e == hipSuccess) {
+        br->slab = f->dn_slab;
+        br->blk = br->slab->base + slot * br->slab->used;
+        br->slab->used += 1, br->slab->live += 1;
+        if (keep_full) e = hipMalloc(&br->Cfull, sizeof(double) * sq);
+    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? -4 : -2, hipGetErrorString(e));
+    DenseFrames fr{};
+    for (int a = 0; a < f->n; ++a) fr.sl[a] = 1.0, fr.sr[a] = tsn[a];
+    if (launch_gather(st, f->n, out->P, f->sm_C, smooth_next->P, out->mean, smooth_next->mean, f->Kg, fr, f->dp,
+                                  br->blk) != 0)
+        return fail(-2, "kernel launch failed");
+    if (keep_full) {
+        e = hipMemcpyAsync(br->Cfull, f->sm_C, sizeof(double) * sq, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return fail(-2, hipGetErrorString(e));
+    }
+    *bridge = br;
+    return 0;
+}
+
+int pnmol_bridge_destroy(pnmol_bridge* b) {
+    if (!b) return -1;
+    b->f->bridges.fetch_sub(1);
+    hipSetDevice(b->f->ctx->device);
+    if (BridgeSlab* sl = b->slab) {
+        sl->live -= 1;
+        if (sl->live == 0) {
+            if (sl == b->f->dn_slab && sl->used < BRIDGE_SLAB_SLOTS) {
+                sl->used = 0;  // (readers and the next writer of a block are on the ctx stream: ordered)
+            } else {
+                if (sl == b->f->dn_slab) b->f->dn_slab = nullptr;
+                (void)hipFree(sl->base);
+                delete sl;
+            }
+        }
+    }
+    if (b->Cfull) (void)hipFree(b->Cfull);
+    delete b;
+    return 0;
+}
+
+int pnmol_bridge_get_interval(const pnmol_bridge* b, double* t, double* dt, int* has_full) {
+    if (!b) return -1;
+    if (t) *t = b->t;
+    if (dt) *dt = b->dt;
+    if (has_full) *has_full = b->Cfull != nullptr;
+    return 0;
+}
+
+namespace {
+
+// (A_th, Q_th): the IWP over the fraction th of a step, in the Nordsieck frame of the whole step (pnmol/base/iwp.py,
+// _partial_interval): entry by entry, every exponent that meets a non-zero entry is >= 0
+void partial_interval(const pnmol_filter* f, double th, double* A, double* Q) {
+    for (int a = 0; a < f->n; ++a)
+        for (int b = 0; b < f->n; ++b) {
+            A[a * MAXN + b] = b >= a ? f->iwp.A1[a * MAXN + b] * std::pow(th, b - a) : 0.0;
+            Q[a * MAXN + b] = f->iwp.Q1[a * MAXN + b] * std::pow(th, 2 * f->nu + 1 - a - b);
+        }
+}
+
+}  // namespace
+
+// pnmol/base/iwp.py, bridge_coefficients: Bp = Q_th A_c^T Q1^-1, M = I - Bp A_c, Bm = M A_th, Qb = M Q_th M^T + Bp Q_c Bp^T
+void bridge_coefficients(const pnmol_filter* f, double th, double* Bm, double* Bp, double* Qb) {
+    const int n = f->n;
+    double A[MAXN * MAXN], Q[MAXN * MAXN], Ac[MAXN * MAXN], Qc[MAXN * MAXN], L[MAXN * MAXN] = {0}, M[MAXN * MAXN];
+    partial_interval(f, th, A, Q);
+    partial_interval(f, 1.0 - th, Ac, Qc);
+    small_cholesky(n, f->iwp.Q1, L);  // (positive definite: cond <= 1.6e4 at n = 4)
+    for (int col = 0; col < n; ++col) {  // column col of X = Q1^-1 (A_c Q_th); Bp = X^T
+        double y[MAXN];
+        for (int a = 0; a < n; ++a) {
+            double v = 0.0;
+            for (int e = 0; e < n; ++e) v += Ac[a * MAXN + e] * Q[e * MAXN + col];
+            y[a] = v;
+        }
+        for (int a = 0; a < n; ++a) {
+            for (int e = 0; e < a; ++e) y[a] -= L[a * MAXN + e] * y[e];
+            y[a] /= L[a * MAXN + a];
+        }
+        for (int a = n - 1; a >= 0; --a) {
+            for (int e = a + 1; e < n; ++e) y[a] -= L[e * MAXN + a] * y[e];
+            y[a] /= L[a * MAXN + a];
+        }
+        for (int a = 0; a < n; ++a) Bp[col * MAXN + a] = y[a];
+    }
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            double v = a == b ? 1.0 : 0.0;
+            for (int e = 0; e < n; ++e) v -= Bp[a * MAXN + e] * Ac[e * MAXN + b];
+            M[a * MAXN + b] = v;
+        }
+    double MQ[MAXN * MAXN], BQ[MAXN * MAXN];
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            double v = 0.0, w = 0.0, u = 0.0;
+            for (int e = 0; e < n; ++e) {
+                v += M[a * MAXN + e] * A[e * MAXN + b];
+                w += M[a * MAXN + e] * Q[e * MAXN + b];
+                u += Bp[a * MAXN + e] * Qc[e * MAXN + b];
+            }
+            Bm[a * MAXN + b] = v, MQ[a * MAXN + b] = w, BQ[a * MAXN + b] = u;
+        }
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            double v = 0.0;
+            for (int e = 0; e < n; ++e) v += MQ[a * MAXN + e] * M[b * MAXN + e] + BQ[a * MAXN + e] * Bp[b * MAXN + e];
+            Qb[a * MAXN + b] = Qb[b * MAXN + a] = v;
+        }
+}
+
+namespace {
+
+int ensure_dense_scratch(pnmol_filter* f, size_t bytes, const char* who) {
+    if (bytes <= f->dn_cap) return 0;
+    if (f->dn_scratch) (void)hipFree(f->dn_scratch);
+    f->dn_scratch = nullptr, f->dn_cap = 0;
+    const hipError_t e = hipMalloc(&f->dn_scratch, bytes);
+    if (e != hipSuccess) {
+        f->ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    f->dn_cap = bytes;
+    return 0;
+}
+
+// table -> device, one launch, the read-out: means / stds (nq, n, d)
+int run_dense_eval(pnmol_filter* f, const double* blk_dev, bool blk_in_scratch, const std::vector<DenseQuery>& table, int one_sided,
+                   double* means, double* stds, const char* who) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t nq = table.size(), no = nq * (size_t)f->n * f->d;
+    const size_t blk_bytes = blk_in_scratch ? sizeof(double) * pnmol_dense_block_doubles(f->n, f->dp) : 0;
+    char* base = static_cast<char*>(f->dn_scratch);
+    double* out_dev = reinterpret_cast<double*>(base + blk_bytes);
+    DenseQuery* tab_dev = reinterpret_cast<DenseQuery*>(base + blk_bytes + 2 * no * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(tab_dev, table.data(), sizeof(DenseQuery) * nq, hipMemcpyHostToDevice, st));
+    if (launch_eval(st, f->n, f->d, f->dp, (int)nq, blk_dev, tab_dev, one_sided, out_dev, out_dev + no) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return -2;
+    }
+    // straight into the caller's arrays (no host staging: at 10 000 queries the read-out is 123 MB), one synchronisation
+    if (means) HIPCHK(ctx, hipMemcpyAsync(means, out_dev, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (stds) HIPCHK(ctx, hipMemcpyAsync(stds, out_dev + no, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
+int pnmol_bridge_eval(const pnmol_bridge* b, int nq, const double* t_q, double* means_qnd, double* stds_qnd) {
+    static const char* who = "pnmol_bridge_eval";
+    if (!b || nq < 1 || !t_q || (!means_qnd && !stds_qnd)) {
+        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, nq < 1)";
+        return -1;
+    }
+    pnmol_filter* f = b->f;
+    pnmol_ctx* ctx = f->ctx;
+    std::vector<DenseQuery> table((size_t)nq);
+    for (int q = 0; q < nq; ++q) {
+        const double t = t_q[q];
+        const bool at_l = times_agree(t, b->t, b->dt), at_r = times_agree(t, b->t + b->dt, b->dt);
+        if (!std::isfinite(t) || (!at_l && !at_r && !(t > b->t && t < b->t + b->dt))) {
+            ctx->err = std::string(who) + ": query time " + std::to_string(t) + " is not inside the bridge's interval [" +
+                       std::to_string(b->t) + ", " + std::to_string(b->t + b->dt) + "]";
+            return -1;
+        }
+        DenseQuery& e = table[(size_t)q];
+        std::memset(&e, 0, sizeof(e));
+        for (int a = 0; a < f->n; ++a) e.sc[a] = nordsieck_scale(f->nu, a, b->dt);
+        const double th = (t - b->t) / b->dt;
+        e.knot = (at_l || !(th > 0.0)) ? 1 : ((at_r || !(th < 1.0)) ? 2 : 0);
+        if (e.knot == 0) {
+            double Qb[MAXN * MAXN];
+            bridge_coefficients(f, th, e.Bm, e.Bp, Qb);
+            for (int a = 0; a < f->n; ++a) e.qbd[a] = Qb[a * MAXN + a];
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t no = (size_t)nq * f->n * f->d;
+    int rc = ensure_dense_scratch(f, 2 * no * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
+    if (rc != 0) return rc;
+    return run_dense_eval(f, b->blk, false, table, 0, means_qnd, stds_qnd, who);
+}
+
+int pnmol_state_predict(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_state* out) {
+    if (!f || !in || !out || in == out || in->f != f || out->f != f || !(dt > 0.0) || !std::isfinite(dt) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = "pnmol_state_predict: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SmoothConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+    for (int a = 0; a < f->n; ++a) c.ts[a] = frame_ratio(f, a, in->frame_dt, dt);
+    if (launch_predict(ctx->stream, f->n, in->P, in->mean, f->Kg, c, f->dp, out->P, out->var, out->mean) != 0) {
+        ctx->err = "pnmol_state_predict: kernel launch failed";
+        return -2;
+    }
+    out->t = in->t + dt;
+    out->frame_dt = dt;
+    return 0;
+}
+
+int pnmol_state_predict_marginals(pnmol_filter* f, const pnmol_state* in, int nq, const double* dt_q, double* means_qnd,
+                                  double* stds_qnd) {
+    static const char* who = "pnmol_state_predict_marginals";
+    if (!f || !in || in->f != f || nq < 1 || !dt_q || (!means_qnd && !stds_qnd) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = std::string(who) + ": bad argument (null, foreign state, nq < 1, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    std::vector<DenseQuery> table((size_t)nq);
+    double sin[MAXN];
+    frame_scales(in, sin);
+    for (int q = 0; q < nq; ++q) {
+        const double dt = dt_q[q];
+        if (!std::isfinite(dt) || dt < 0.0) {
+            ctx->err = std::string(who) + ": dt_q[" + std::to_string(q) + "] = " + std::to_string(dt) + " is negative or not finite";
+            return -1;
+        }
+        DenseQuery& e = table[(size_t)q];
+        std::memset(&e, 0, sizeof(e));
+        if (dt == 0.0) {  // the state itself
+            e.knot = 1;
+            for (int a = 0; a < f->n; ++a) e.sc[a] = sin[a];
+            continue;
+        }
+        // frame of dt: x_t ~ N(A1 (ts o m), A1 (ts ts^T o P) A1^T + Q1 (x) K), ts = frame change of the input
+        for (int a = 0; a < f->n; ++a) {
+            e.sc[a] = nordsieck_scale(f->nu, a, dt);
+            e.qbd[a] = f->iwp.Q1[a * MAXN + a];
+            for (int b2 = 0; b2 < f->n; ++b2) e.Bm[a * MAXN + b2] = f->iwp.A1[a * MAXN + b2] * (sin[b2] / nordsieck_scale(f->nu, b2, dt));
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t no = (size_t)nq * f->n * f->d, nb = pnmol_dense_block_doubles(f->n, f->dp);
+    int rc = ensure_dense_scratch(f, (nb + 2 * no) * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
+    if (rc != 0) return rc;
+    double* blk = static_cast<double*>(f->dn_scratch);
+    DenseFrames fr{};
+    for (int a = 0; a < f->n; ++a) fr.sl[a] = fr.sr[a] = 1.0;  // (the block stays in the state's frame; Bm carries the change)
+    if (launch_gather(ctx->stream, f->n, in->P, nullptr, nullptr, in->mean, nullptr, f->Kg, fr, f->dp, blk) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return -2;
+    }
+    return run_dense_eval(f, blk, true, table, 1, means_qnd, stds_qnd, who);
+}
+
+int pnmol_bridge_state(const pnmol_bridge* b, const pnmol_state* smooth_k, const pnmol_state* smooth_next, double t,
+                       pnmol_state* out) {
+    static const char* who = "pnmol_bridge_state";
+    if (!b || !smooth_k || !smooth_next || !out || out == smooth_k || out == smooth_next || smooth_k->f != b->f ||
+        smooth_next->f != b->f || out->f != b->f) {
+        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, aliasing, state of another filter)";
+        return -1;
+    }
+    pnmol_filter* f = b->f;
+    pnmol_ctx* ctx = f->ctx;
+    if (!b->Cfull) {
+        ctx->err = std::string(who) + ": this bridge was made without keep_full (no cross-covariance C_k)";
+        return -1;
+    }
+    if (!times_agree(smooth_k->t, b->t, b->dt) || !times_agree(smooth_next->t, b->t + b->dt, b->dt)) {
+        ctx->err = std::string(who) + ": the states sit at t = " + std::to_string(smooth_k->t) + " and " +
+                   std::to_string(smooth_next->t) + ", not at the two ends of the bridge's interval";
+        return -1;
+    }
+    const double th = (t - b->t) / b->dt;
+    if (!std::isfinite(t) || !(th > 0.0) || !(th < 1.0)) {
+        ctx->err = std::string(who) + ": t = " + std::to_string(t) + " is not strictly inside the bridge's interval (at its ends "
+                   "the posterior is the state given)";
+        return -1;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DenseMix c{};
+    bridge_coefficients(f, th, c.Bm, c.Bp, c.Qb);
+    for (int a = 0; a < f->n; ++a)
+        for (int e = 0; e < f->n; ++e) {
+            c.BmS[a * MAXN + e] = c.Bm[a * MAXN + e] * frame_ratio(f, e, smooth_k->frame_dt, b->dt);
+            c.BpS[a * MAXN + e] = c.Bp[a * MAXN + e] * frame_ratio(f, e, smooth_next->frame_dt, b->dt);
+        }
+    const double* ml = b->blk + 3 * (size_t)f->n * f->n * f->dp;
+    if (launch_state(ctx->stream, f->n, smooth_k->P, smooth_next->P, b->Cfull, f->Kg, ml, ml + (size_t)f->n * f->dp, c,
+                                 f->dp, out->P, out->var, out->mean) != 0) {
+        ctx->err = std::string(who) + ": kernel launch failed";
+        return -2;
+    }
+    out->t = t;
+    out->frame_dt = b->dt;
+    return 0;
 }

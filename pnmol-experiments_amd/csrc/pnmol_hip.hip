@@ -37,16 +37,8 @@
 
 namespace {
 
-constexpr int NB = 32;        // factorisation block
 constexpr int TLD = NB + 1;   // LDS leading dimension of a 32x32 tile (bank-conflict pad)
-constexpr int MAXN = 4;       // max derivatives + 1
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-struct IwpConsts {
-    double A1[MAXN * MAXN];  // flip(pascal_lower)  base/iwp.py:24-27
-    double Q1[MAXN * MAXN];  // flip(hilbert)       base/iwp.py:29
-    double ts[MAXN];         // frame change  s_old[a] / s_new[a]
-};
 
 // ------------------------------------------------------------------------------------------
 // H apply (stencil gather).  ELL arrays are [e*mp + i].
@@ -3254,29 +3246,11 @@ __global__ __launch_bounds__(128) void k_fd_solve(const double* __restrict__ gra
     unc[p] = llk[p] - dot;
 }
 
-// ------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------
-#define HIPCHK(ctx, call)                                                                        \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return -2;                                                                           \
-        }                                                                                        \
-    } while (0)
-
-static inline int round_up(int x, int q) { return (x + q - 1) / q * q; }
-
-static double nordsieck_scale(int nu, int a, double dt) {  // base/iwp.py:55-62
-    double fact = 1.0;
-    for (int q = 2; q <= nu - a; ++q) fact *= q;
-    return std::pow(std::fabs(dt), nu - a + 0.5) / fact;
-}
-
 }  // namespace
 
-// struct pnmol_ctx: pnmol_internal.hpp
+// ------------------------------------------------------------------------------------------
+// host side (HIPCHK, the handle structs and what else the files under csrc/ share: pnmol_internal.hpp)
+// ------------------------------------------------------------------------------------------
 
 // ------------------------------------------------------------------------------------------
 // Large problems (the 64x64 mesh of BASELINE config 5: D = 8192, m = 4348): P = P- - W W^T as ONE plain SYRK over the D x D
@@ -3472,139 +3446,6 @@ __global__ __launch_bounds__(256, 2) void k_w_gemm(const double* __restrict__ A,
 __global__ __launch_bounds__(256) void k_vecops(VecArgs va, const double* __restrict__ W, int mp, long Dp, int per_row) {
     vecops_rows(va, W, mp, Dp, ((long)blockIdx.y * per_row + blockIdx.x) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
-
-struct pnmol_filter {
-    pnmol_ctx* ctx = nullptr;
-    int d = 0, n = 0, nu = 0, nB = 0, m = 0, dp = 0, mp = 0, CB = 0, RBS = 0, RBW = 0, RT = 0, ellw = 0;
-    int* tickets = nullptr;   // device: read-out blocks that have taken their slot (k_readout with the next step's role)
-    int* last_ctr = nullptr;  // device: step-counter value of the last step of the running pnmol_filter_steps call
-    int fuse_predict = 1;     // PNMOL_HIP_FUSE_PREDICT: predict the next step's covariance in the down-date epilogue
-    int* flags = nullptr;  // k_sweep dependency flags: row[RT], diag[CB], abort, claim[CB*CB] (helpers); k_sweep_rl: rl_flags()
-    int nflags = 0;        // words allocated (all of them are zeroed before every sweep)
-    double* hs_scratch = nullptr;  // helpers' partial sums, one tile per (row, target step)
-    int w_gemm = 0;        // ... and W = (P- H^T) Ls^-T as a GEMM behind a sweep without the rows of W (k_w_gemm)
-    int dd_big = 0;        // large problems: sweep alone + k_downdate_big (PNMOL_HIP_DD_BIG=0/1 overrides; see there)
-    int sweep_mode = 2;    // PNMOL_HIP_SWEEP: 2 = k_sweep with the covariance down-date riding along in the same launch,
-                           // 1 = k_sweep, then k_downdate; 0 = k_diag0 + one k_panel launch per panel, then k_downdate
-    int ds = 0;  // spatial components of the state (= d, or 2d for the latent-force model [u; eps])
-    bool counted = false;  // this filter is in live_rl_filters[device]
-    bool registered = false;  // this filter is counted in ctx->children
-    std::atomic<int> states{0};  // live pnmol_state objects of this filter (pnmol_filter_destroy refuses while > 0)
-    int xcd_home = -1;  // k_sweep_rl: >= 0: XCD-local layout (XL), chain workgroup and S row blocks on this XCD; -1: spread layout
-    int p32 = 0;        // pnmol_filter_desc.dtype = 1: covariances (state, predicted, Q) are stored and down-dated in fp32
-    size_t psz = 8;     // bytes per covariance element
-    long Dp = 0;
-    IwpConsts iwp{};
-    int* ell_col = nullptr;
-    double* ell_val = nullptr;
-    // the operator given at creation (pde.L), kept for pnmol_filter_set_operator_diagonal: its ELL image, the slot of the
-    // diagonal entry of every PDE row (-1: the row has none), and a pinned staging buffer [jdiag d | shift mp]
-    int* ell_col_base = nullptr;
-    double* ell_val_base = nullptr;
-    int* ell_diag_slot = nullptr;
-    int base_w = 0, base_has_diag = 0;
-    int ell_is_base = 1;      // ell_col / ell_val hold the base image (diagonal slots aside): no dense upload since the last restore
-    double* h_op = nullptr;
-    double* h_op_dev = nullptr;
-    hipEvent_t ev_op = nullptr;
-    double *Kg = nullptr, *rdiag = nullptr, *Rdense = nullptr, *shift = nullptr;
-    double *G = nullptr, *F = nullptr, *Linv = nullptr, *Ppred = nullptr, *mpred = nullptr, *zbuf = nullptr;
-    double *var = nullptr, *Sqinv = nullptr, *rec = nullptr, *part = nullptr, *sdiag = nullptr;
-    int* info = nullptr;
-    std::vector<double> sqdiag;
-    double* Qfull = nullptr;  // Q1 (x) K as a dense Dp x Dp matrix (on-device error model), allocated on first use
-    int* one = nullptr;       // device constant 1 (step-counter stand-in for sweeps outside the step loop)
-    int* info_err = nullptr;  // info word of those sweeps
-    double sq_dt = -1.0;
-    std::vector<double> hB;   // host copy of pde.B (nB x d) for operator rebuilds
-    int ell_cap = 0;          // allocated ELL width
-    // scratch state for ping-pong inside steps()
-    double *tmpP = nullptr, *tmpMean = nullptr;
-    double *rec_means = nullptr, *rec_stds = nullptr;
-    double* h_pin = nullptr;  // pinned host staging: [rec 4k | means k*d | stds k*d | info k ints]
-    double* h_pin_dev = nullptr;  // the same buffer as the device sees it (mapped)
-    int rec_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = 0.f;
-    int* ctr = nullptr;  // device step counter (slot of the per-step outputs)
-    int pending_k = 0;   // steps enqueued by pnmol_filter_steps_begin and not yet collected
-    double pending_dt = 0.0;
-    pnmol_state* pending_state = nullptr;
-    struct GraphEntry {
-        double *P0, *P1, *var;
-        double dt;
-        int nsteps;
-        bool have_sq;
-        bool fused;
-        hipGraphExec_t exec;
-        bool launched;  // the first launch of an executable graph costs ~50 ms of host time (ROCm 7.2)
-    };
-    std::vector<GraphEntry> graphs;
-    int graph_chunk = 10;  // steps per captured graph (even); 0 disables graphs
-    // RTS smoother (pnmol_smoother_step), allocated on first use: the sweep's tall matrices [P-; P A^T; 0; I] -> [L; V; 0; T]
-    // ((3 Dp/32 + 1) * 32 x Dp), its L_jj^-1 tiles, feed tiles and flags, and G, C, Ps^h (Dp x Dp), [m^h | dm] (2 Dp)
-    double *sm_G = nullptr, *sm_F = nullptr, *sm_Linv = nullptr, *sm_hs = nullptr, *sm_gain = nullptr, *sm_C = nullptr,
-           *sm_Psh = nullptr, *sm_vec = nullptr;
-    int *sm_flags = nullptr, *sm_info = nullptr;
-    int sm_nflags = 0;
-    // Joint draws (pnmol_samples_*), allocated on first use: the square lenient sweep P^h -> C (sp_Gc, sp_F: Dp x Dp, its
-    // L_jj^-1 tiles, feed tiles, flags, info word), Gamma (dp x dp, from the host copy kept at creation) and m^h (Dp).  The
-    // main sweep of a backward step runs in the smoother's workspace above.
-    double *sp_Gc = nullptr, *sp_F = nullptr, *sp_Linv = nullptr, *sp_hs = nullptr, *sp_Gamma = nullptr, *sp_mh = nullptr;
-    int *sp_flags = nullptr, *sp_info = nullptr;
-    int sp_nflags = 0;
-    // a backward step has two independent sweeps (P^h -> C and [P-; P A^T; 0; I]): on wide problems the second one runs on
-    // this side stream, between the two events, while the ctx stream factorises P^h and forms xt and r
-    hipStream_t sp_stream = nullptr;
-    hipEvent_t sp_ev_built = nullptr, sp_ev_swept = nullptr;
-    std::vector<double> hGamma;        // desc->Gamma padded to dp x dp (white-noise fp64 filters)
-    std::atomic<int> samples{0};       // live pnmol_samples objects of this filter (pnmol_filter_destroy refuses while > 0)
-    // Dense output (pnmol_bridge_*, pnmol_state_predict_marginals): scratch for the query table and the read-out, grown on demand
-    std::atomic<int> bridges{0};       // live pnmol_bridge objects of this filter (pnmol_filter_destroy refuses while > 0)
-    void* dn_scratch = nullptr;
-    size_t dn_cap = 0;
-    struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
-};
-
-struct pnmol_state {
-    pnmol_filter* f = nullptr;
-    double* mean = nullptr;  // Dp
-    double* P = nullptr;     // Dp*Dp
-    double* var = nullptr;   // Dp   marginal variances, same frame as P
-    double t = 0.0;
-    double frame_dt = 0.0;  // 0 = raw coordinates, else Nordsieck frame of that dt
-};
-
-// The blocks of a filter's bridges come out of slabs of BRIDGE_SLAB_SLOTS blocks: smooth() makes one bridge per step, and a device
-// allocation per step is what the bridges would otherwise cost most.  A slab is freed when the last bridge in it is destroyed (the
-// filter's current slab is reused instead while it has free slots).
-constexpr int BRIDGE_SLAB_SLOTS = 64;
-struct BridgeSlab {
-    double* base = nullptr;
-    int used = 0;  // slots handed out
-    int live = 0;  // bridges alive
-};
-
-struct pnmol_bridge {
-    pnmol_filter* f = nullptr;
-    BridgeSlab* slab = nullptr;
-    double* blk = nullptr;    // point-diagonal blocks of Ps_k, C_k, Ps_{k+1}, the two means, diag K (pnmol_dense_block_doubles): a slot of slab
-    double* Cfull = nullptr;  // C_k (Dp x Dp), kept on request
-    double t = 0.0, dt = 0.0; // the interval [t, t + dt]; everything above is in the Nordsieck frame of dt
-};
-
-struct pnmol_samples {
-    pnmol_filter* f = nullptr;
-    int S = 0, Sp = 0;       // draws, padded to a multiple of 64
-    double* X = nullptr;     // Dp x Sp: the draws at time t, in the frame frame_dt
-    double* Xi = nullptr;    // 2 Dp x Sp: noise [xi_1; xi_2]
-    double* Xt = nullptr;    // Dp x Sp: xt = m + s C xi_1
-    double* R = nullptr;     // Dp x Sp: Gamma xi_2 per derivative block, then T^T r
-    double* Y = nullptr;     // Dp x Sp: r
-    double* stage = nullptr; // S x 2D: host-supplied noise / read-out, allocated on first use
-    double t = 0.0, frame_dt = 0.0;
-    bool drawn = false;
-};
 
 namespace {
 
@@ -3954,15 +3795,6 @@ void fill_out(const pnmol_filter* f, const double* rec, int info, double t_new, 
 }
 
 template <int N>
-int run_cov_sqrtm_sweep(pnmol_filter* f, const double* Gc, double* Fc, double* Linvc, int Dq, double* feedc) {
-    DowndateArgs dd{};
-    const int cb = Dq / NB;
-    launch_sweep<N, false>(cb, f->ctx->stream, Gc, Fc, Linvc, Dq, cb, cb, f->flags, f->info_err, f->one, dd,
-                           f->flags + 2 * cb + 1, cb <= 17 && sweep_rl_enabled() ? feedc : f->hs_scratch, 1, f->xcd_home);
-    return 0;
-}
-
-template <int N>
 int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
     hipStream_t st = f->ctx->stream;
     const int mp = f->mp;
@@ -3975,162 +3807,73 @@ int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
     return 0;
 }
 
-// ---- RTS smoother (pnmol_smoother_step; kernels in pnmol_smooth.hip) --------------------------------------------------
-// The tall matrix of the backward step has the error model's layout with Dp columns: [P- (cb); P A^T (cb); zero block; I (cb)],
-// so the forward step's sweep launch factorises it as it is (strict pivots: P- >= Q1 (x) K is positive definite; the padded
-// points carry a unit pivot).
-void free_smoother_ws(pnmol_filter* f) {
-    for (void* p : {(void*)f->sm_G, (void*)f->sm_F, (void*)f->sm_Linv, (void*)f->sm_hs, (void*)f->sm_gain, (void*)f->sm_C,
-                    (void*)f->sm_Psh, (void*)f->sm_vec, (void*)f->sm_flags, (void*)f->sm_info})
-        if (p) (void)hipFree(p);
-    f->sm_G = f->sm_F = f->sm_Linv = f->sm_hs = f->sm_gain = f->sm_C = f->sm_Psh = f->sm_vec = nullptr;
-    f->sm_flags = f->sm_info = nullptr;
-}
+}  // namespace
 
-int ensure_smoother_ws(pnmol_filter* f) {
-    if (f->sm_G) return 0;
-    pnmol_ctx* ctx = f->ctx;
-    const long Dp = f->Dp;
-    const int cb = (int)(Dp / NB), rt = 3 * cb + 1;
-    const size_t tall = (size_t)rt * NB * Dp, sq = (size_t)Dp * Dp;
-    f->sm_nflags = std::max(rt + cb + 1 + cb * cb, rl_flags(rt, cb).total);
-    hipError_t e = hipSuccess;
-    auto al = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-    };
-    al((void**)&f->sm_G, sizeof(double) * tall);
-    al((void**)&f->sm_F, sizeof(double) * tall);
-    al((void**)&f->sm_Linv, sizeof(double) * (size_t)cb * NB * NB);
-    al((void**)&f->sm_hs, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
-    al((void**)&f->sm_gain, sizeof(double) * sq);
-    al((void**)&f->sm_C, sizeof(double) * sq);
-    al((void**)&f->sm_Psh, sizeof(double) * sq);
-    al((void**)&f->sm_vec, sizeof(double) * 2 * (size_t)Dp);
-    al((void**)&f->sm_flags, sizeof(int) * (size_t)f->sm_nflags);
-    al((void**)&f->sm_info, sizeof(int));
-    if (e == hipSuccess && !f->one) {
-        al((void**)&f->one, sizeof(int));
-        al((void**)&f->info_err, sizeof(int));
-        const int h1 = 1;
-        if (e == hipSuccess) e = hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice);
-    }
-    // (the zero block and the identity rows of sm_G, and the parts of sm_F / sm_Linv the sweep never writes, stay as set here)
-    if (e == hipSuccess) e = hipMemsetAsync(f->sm_G, 0, sizeof(double) * tall, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f->sm_F, 0, sizeof(double) * tall, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f->sm_Linv, 0, sizeof(double) * (size_t)cb * NB * NB, ctx->stream);
-    if (e == hipSuccess) {
-        k_set_identity<<<(unsigned)((Dp + 255) / 256), 256, 0, ctx->stream>>>(f->sm_G + (2 * Dp + NB) * Dp, (int)Dp);
+// ---- the sweep workspace of the callers outside the filter step (pnmol_internal.hpp) ---------------------------------------
+hipError_t sweep_ws_alloc(SweepWs* w, pnmol_ctx* ctx, int rt, int cb) {
+    const int ld = cb * NB;
+    const size_t mat = (size_t)rt * NB * ld, linv = (size_t)cb * NB * NB;
+    w->rt = rt, w->cb = cb, w->ld = ld;
+    w->left_looking = !(sweep_rl_enabled() && cb <= 17);
+    // k_sweep: row[rt], diag[cb], abort, claim[cb * cb];  k_sweep_rl: rl_flags()
+    w->nflags = std::max(rt + cb + 1 + cb * cb, rl_flags(rt, cb).total);
+    hipError_t e = hipMalloc(&w->G, sizeof(double) * mat);
+    if (e == hipSuccess) e = hipMalloc(&w->F, sizeof(double) * mat);
+    if (e == hipSuccess) e = hipMalloc(&w->Linv, sizeof(double) * linv);
+    if (e == hipSuccess) e = hipMalloc(&w->feed, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
+    if (e == hipSuccess) e = hipMalloc(&w->flags, sizeof(int) * (size_t)w->nflags);
+    if (e == hipSuccess) e = hipMalloc(&w->info, sizeof(int));
+    if (e == hipSuccess && rt > cb) e = hipMemsetAsync(w->G, 0, sizeof(double) * mat, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w->F, 0, sizeof(double) * mat, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w->Linv, 0, sizeof(double) * linv, ctx->stream);
+    if (e == hipSuccess && rt > cb) {
+        k_set_identity<<<(unsigned)((ld + 255) / 256), 256, 0, ctx->stream>>>(w->G + (size_t)(rt - cb) * NB * ld, ld);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        ctx->err = std::string("pnmol_smoother_step: workspace: ") + hipGetErrorString(e);
-        free_smoother_ws(f);
-        return e == hipErrorOutOfMemory ? -4 : -2;
-    }
-    return 0;
+    if (e != hipSuccess) sweep_ws_free(w);
+    return e;
 }
 
-template <int N>
-void run_smoother_sweep(pnmol_filter* f, hipStream_t st = nullptr) {
-    const int cb = (int)(f->Dp / NB), rt = 3 * cb + 1;
-    DowndateArgs dd{};
-    launch_sweep<N, false>(rt, st ? st : f->ctx->stream, f->sm_G, f->sm_F, f->sm_Linv, (int)f->Dp, cb, rt, f->sm_flags, f->sm_info, f->one,
-                           dd, f->sm_flags + rt + cb + 1, f->sm_hs, 0, f->xcd_home);
-}
-
-// ---- joint draws (pnmol_samples_*; kernels in pnmol_sample.hip) ----------------------------------------------------------
-void free_sampler_ws(pnmol_filter* f) {
-    for (void* p : {(void*)f->sp_Gc, (void*)f->sp_F, (void*)f->sp_Linv, (void*)f->sp_hs, (void*)f->sp_Gamma, (void*)f->sp_mh,
-                    (void*)f->sp_flags, (void*)f->sp_info})
+void sweep_ws_free(SweepWs* w) {
+    for (void* p : {(void*)w->G, (void*)w->F, (void*)w->Linv, (void*)w->feed, (void*)w->flags, (void*)w->info})
         if (p) (void)hipFree(p);
-    f->sp_Gc = f->sp_F = f->sp_Linv = f->sp_hs = f->sp_Gamma = f->sp_mh = nullptr;
-    f->sp_flags = f->sp_info = nullptr;
-    if (f->sp_ev_built) (void)hipEventDestroy(f->sp_ev_built);
-    if (f->sp_ev_swept) (void)hipEventDestroy(f->sp_ev_swept);
-    if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
-    f->sp_ev_built = f->sp_ev_swept = nullptr;
-    f->sp_stream = nullptr;
+    *w = SweepWs{};
 }
 
-int ensure_sampler_ws(pnmol_filter* f, const char* who) {
-    if (f->sp_Gc) return 0;
-    pnmol_ctx* ctx = f->ctx;
-    const long Dp = f->Dp;
-    const int cb = (int)(Dp / NB);
-    const size_t sq = (size_t)Dp * Dp, gq = (size_t)f->dp * f->dp;
-    f->sp_nflags = std::max(2 * cb + 1 + cb * cb, rl_flags(cb, cb).total);
-    hipError_t e = hipSuccess;
-    auto al = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-    };
-    al((void**)&f->sp_Gc, sizeof(double) * sq);
-    al((void**)&f->sp_F, sizeof(double) * sq);
-    al((void**)&f->sp_Linv, sizeof(double) * (size_t)cb * NB * NB);
-    al((void**)&f->sp_hs, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
-    al((void**)&f->sp_Gamma, sizeof(double) * gq);
-    al((void**)&f->sp_mh, sizeof(double) * (size_t)Dp);
-    al((void**)&f->sp_flags, sizeof(int) * (size_t)f->sp_nflags);
-    al((void**)&f->sp_info, sizeof(int));
-    if (e == hipSuccess && !f->one) {
-        al((void**)&f->one, sizeof(int));
-        al((void**)&f->info_err, sizeof(int));
-        const int h1 = 1;
-        if (e == hipSuccess) e = hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice);
-    }
-    // (the tiles of sp_F above the diagonal and the parts of sp_Linv the sweep never writes stay as set here)
-    if (e == hipSuccess) e = hipMemsetAsync(f->sp_F, 0, sizeof(double) * sq, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f->sp_Linv, 0, sizeof(double) * (size_t)cb * NB * NB, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(f->sp_Gamma, f->hGamma.data(), sizeof(double) * gq, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->sp_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->sp_ev_built, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->sp_ev_swept, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        ctx->err = std::string(who) + ": workspace: " + hipGetErrorString(e);
-        free_sampler_ws(f);
-        return e == hipErrorOutOfMemory ? -4 : -2;
-    }
-    return 0;
-}
-
-// P^h (in sp_Gc) -> C (in sp_F), dropped-pivot rule of pnmol_state_get_cov_sqrtm
+namespace {
 template <int N>
-void run_sampler_factor_sweep(pnmol_filter* f) {
-    const int cb = (int)(f->Dp / NB);
-    DowndateArgs dd{};
-    launch_sweep<N, false>(cb, f->ctx->stream, f->sp_Gc, f->sp_F, f->sp_Linv, (int)f->Dp, cb, cb, f->sp_flags, f->sp_info, f->one,
-                           dd, f->sp_flags + 2 * cb + 1, f->sp_hs, 1, f->xcd_home);
+void run_ws_sweep(const pnmol_filter* f, const SweepWs& w, hipStream_t st, int lenient) {
+    const DowndateArgs dd{};
+    // (k_sweep's claim words lie behind row[rt], diag[cb] and the abort word)
+    launch_sweep<N, false>(w.rt, st, w.G, w.F, w.Linv, w.ld, w.cb, w.rt, w.flags, w.info, f->one, dd, w.flags + w.rt + w.cb + 1, w.feed,
+                           lenient, f->xcd_home);
 }
+}  // namespace
 
-int enqueue_sampler_factor(pnmol_filter* f, const char* who) {
+int sweep_ws_enqueue(pnmol_filter* f, const SweepWs& w, hipStream_t st, int lenient, const char* who) {
     pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipMemsetAsync(f->sp_flags, 0, sizeof(int) * f->sp_nflags, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(f->sp_info, 0x7f, sizeof(int), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(w.flags, 0, sizeof(int) * w.nflags, st));
+    HIPCHK(ctx, hipMemsetAsync(w.info, 0x7f, sizeof(int), st));
     switch (f->n) {
-        case 2: run_sampler_factor_sweep<2>(f); break;
-        case 3: run_sampler_factor_sweep<3>(f); break;
-        case 4: run_sampler_factor_sweep<4>(f); break;
+        case 2: run_ws_sweep<2>(f, w, st, lenient); break;
+        case 3: run_ws_sweep<3>(f, w, st, lenient); break;
+        case 4: run_ws_sweep<4>(f, w, st, lenient); break;
         default: ctx->err = std::string(who) + ": unsupported number of derivatives"; return -1;
     }
     return 0;
 }
 
-// the noise block of a call: host-supplied (rows of `cols` components) or generated on the device
-int fill_noise(pnmol_samples* x, const double* xi, int cols, unsigned long long seed, unsigned long long step_index, const char* who) {
-    pnmol_filter* f = x->f;
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    int rc;
-    if (xi) {
-        HIPCHK(ctx, hipMemcpyAsync(x->stage, xi, sizeof(double) * (size_t)x->S * cols, hipMemcpyHostToDevice, st));
-        rc = pnmol_sample_launch_scatter(st, x->stage, x->S, cols, f->d, f->dp, f->n, x->Sp, x->Xi);
-    } else {
-        rc = pnmol_sample_launch_noise(st, seed, step_index, x->S, cols, f->d, f->dp, f->n, x->Sp, x->Xi, nullptr);
+int sweep_info_result(pnmol_ctx* ctx, int inf, long limit, const char* who, const char* what, const char* wait) {
+    if (inf == -2) {
+        ctx->err = std::string(who) + ": " + wait;
+        return -2;
     }
-    if (rc != 0) ctx->err = std::string(who) + ": kernel launch failed";
-    return rc;
+    if (inf < limit) {
+        ctx->err = std::string(who) + ": " + what + " at pivot " + std::to_string(inf);
+        return -3;
+    }
+    return 0;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -4255,14 +3998,7 @@ int pnmol_cholesky_lower(pnmol_ctx* ctx, const double* A_nn, int n, double* L_nn
         ctx->err = std::string("pnmol_cholesky_lower: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? -4 : -2;
     }
-    if (inf == -2) {
-        ctx->err = "pnmol_cholesky_lower: a dependency wait timed out";
-        return -2;
-    }
-    if (inf < Dq) {
-        ctx->err = "pnmol_cholesky_lower: matrix not positive definite at pivot " + std::to_string(inf);
-        return -3;
-    }
+    if (int rc = sweep_info_result(ctx, inf, Dq, "pnmol_cholesky_lower", "matrix not positive definite")) return rc;
     for (int i = 0; i < n; ++i) {
         std::memcpy(L_nn + (size_t)i * n, &hG[(size_t)i * Dq], sizeof(double) * (i + 1));
         for (int k = i + 1; k < n; ++k) L_nn[(size_t)i * n + k] = 0.0;
@@ -4399,6 +4135,12 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
     FCHK(hipMalloc(&f->zbuf, sizeof(double) * mp));
     FCHK(hipMalloc(&f->part, sizeof(double) * 3 * mp));
     FCHK(hipMalloc(&f->ctr, sizeof(int)));
+    {
+        const int h1 = 1;
+        FCHK(hipMalloc(&f->one, sizeof(int)));
+        FCHK(hipMalloc(&f->info_err, sizeof(int)));
+        FCHK(hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice));
+    }
     if (const char* gc = std::getenv("PNMOL_HIP_GRAPH_CHUNK")) f->graph_chunk = std::atoi(gc) / 2 * 2;
     if (const char* e = std::getenv("PNMOL_HIP_SWEEP")) f->sweep_mode = std::atoi(e);
     if (f->sweep_mode == 2 && n > 3) f->sweep_mode = 1;  // the fused down-date role is built for n <= 3
@@ -4430,8 +4172,8 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
         }
     }
     FCHK(hipMalloc(&f->sdiag, sizeof(double) * (mp + 1)));
-    // k_sweep: row[RT], diag[CB], abort, claim[CB*CB];  k_sweep_rl: rl_flags();  the Cholesky factor of a whole
-    // covariance (pnmol_state_get_cov_sqrtm) runs a square sweep of up to Dp/32 blocks on the same words
+    // k_sweep: row[RT], diag[CB], abort, claim[CB*CB];  k_sweep_rl: rl_flags();  (the third term dates from the time when
+    // pnmol_state_get_cov_sqrtm ran its square sweep on these words; it stays because the size is baked into captured graphs)
     f->nflags = std::max({f->RT + f->CB + 1 + f->CB * f->CB, rl_flags(f->RT, f->CB).total,
                           rl_flags((int)(f->Dp / NB) + 1, (int)(f->Dp / NB) + 1).total});
     FCHK(hipMalloc(&f->flags, sizeof(int) * f->nflags));
@@ -4508,11 +4250,6 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     if (f->registered) f->ctx->children.fetch_sub(1);
     hipSetDevice(f->ctx->device);
     drop_graphs(f);
-    if (f->dn_scratch) hipFree(f->dn_scratch);
-    if (f->dn_slab) {  // (no bridge is alive: the slab is empty)
-        if (f->dn_slab->base) hipFree(f->dn_slab->base);
-        delete f->dn_slab;
-    }
     if (f->ctr) hipFree(f->ctr);
     if (f->h_pin) hipHostFree(f->h_pin);
     void* ptrs[] = {f->ell_col, f->ell_val, f->Kg,   f->rdiag,   f->Rdense, f->shift,     f->G,        f->F,
@@ -4524,8 +4261,9 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     if (f->ev_op) hipEventDestroy(f->ev_op);
     for (void* q : {(void*)f->ell_col_base, (void*)f->ell_val_base, (void*)f->ell_diag_slot})
         if (q) hipFree(q);
-    free_smoother_ws(f);
-    free_sampler_ws(f);
+    pnmol_smooth_free_ws(f);
+    pnmol_sample_free_ws(f);
+    pnmol_dense_free_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -4572,12 +4310,6 @@ int pnmol_filter_prepare_error_model(pnmol_filter* f, double dt) {
     hipStream_t st = ctx->stream;
     const int mp = f->mp, m = f->m, dp = f->dp;
     const long Dp = f->Dp;
-    if (!f->one) {  // (pnmol_state_get_cov_sqrtm may have made them already: found by the sanitizer run, tests/asan)
-        HIPCHK(ctx, hipMalloc(&f->one, sizeof(int)));
-        HIPCHK(ctx, hipMalloc(&f->info_err, sizeof(int)));
-        const int h1 = 1;
-        HIPCHK(ctx, hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice));
-    }
     if (!f->Qfull) {
         HIPCHK(ctx, hipMalloc(&f->Qfull, f->psz * (size_t)Dp * Dp));
         k_fill_q<<<(unsigned)((Dp * Dp + 255) / 256), 256, 0, st>>>(f->Qfull, f->Kg, f->iwp, f->n, dp, f->p32);
@@ -4608,11 +4340,7 @@ int pnmol_filter_prepare_error_model(pnmol_filter* f, double dt) {
         ctx->err = std::string("prepare_error_model: ") + hipGetErrorString(e);
         return -2;
     }
-    if (inf < mp) {
-        ctx->err = inf == -2 ? "prepare_error_model: a dependency wait timed out"
-                             : "prepare_error_model: Sq not positive definite at pivot " + std::to_string(inf);
-        return inf == -2 ? -2 : -3;
-    }
+    if (int rc = sweep_info_result(ctx, inf, mp, "prepare_error_model", "Sq not positive definite")) return rc;
     f->sqdiag = hd;
     f->sq_dt = dt;
     if (fresh) drop_graphs(f);
@@ -4862,10 +4590,6 @@ int pnmol_state_get_time(const pnmol_state* s, double* t) {
     return 0;
 }
 
-static void frame_scales(const pnmol_state* s, double* sc) {
-    for (int a = 0; a < s->f->n; ++a) sc[a] = s->frame_dt == 0.0 ? 1.0 : nordsieck_scale(s->f->nu, a, s->frame_dt);
-}
-
 int pnmol_state_get_mean(const pnmol_state* s, double* mean_nd) {
     if (!s || !mean_nd) return -1;
     pnmol_filter* f = s->f;
@@ -4890,62 +4614,34 @@ int pnmol_state_get_cov_sqrtm(const pnmol_state* s, double* C_DD) {
     const int n = f->n, d = f->ds;
     const long D = (long)n * d;
     const int Dq = round_up((int)D, NB), cb = Dq / NB;
-    if (std::max(2 * cb + 1, rl_flags(cb, cb).total) > f->nflags) {
-        ctx->err = "pnmol_state_get_cov_sqrtm: flag buffer too small for this shape";
-        return -1;
-    }
-    double *Gc = nullptr, *Fc = nullptr, *Lc = nullptr, *dsc = nullptr, *feedc = nullptr;
-    hipError_t e = hipMalloc(&Gc, sizeof(double) * (size_t)Dq * Dq);
-    if (e == hipSuccess) e = hipMalloc(&feedc, sizeof(double) * (size_t)(2 * cb + 2) * NB * NB);
-    if (e == hipSuccess) e = hipMalloc(&Fc, sizeof(double) * (size_t)Dq * Dq);
-    if (e == hipSuccess) e = hipMalloc(&Lc, sizeof(double) * (size_t)cb * NB * NB);
+    SweepWs ws;
+    double* dsc = nullptr;
+    hipError_t e = sweep_ws_alloc(&ws, ctx, cb, cb);
     if (e == hipSuccess) e = hipMalloc(&dsc, sizeof(double) * MAXN);
-    if (e == hipSuccess && !f->one) {
-        e = hipMalloc(&f->one, sizeof(int));
-        if (e == hipSuccess) e = hipMalloc(&f->info_err, sizeof(int));
-        const int h1 = 1;
-        if (e == hipSuccess) e = hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice);
-    }
     int rc = 0, inf = 0;
     std::vector<double> hF;
     if (e == hipSuccess) {
         double sc[MAXN];
         frame_scales(s, sc);
         e = hipMemcpy(dsc, sc, sizeof(double) * MAXN, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemsetAsync(Fc, 0, sizeof(double) * (size_t)Dq * Dq, st);
-        if (e == hipSuccess) e = hipMemsetAsync(Lc, 0, sizeof(double) * (size_t)cb * NB * NB, st);
-        if (e == hipSuccess) e = hipMemsetAsync(f->flags, 0, sizeof(int) * f->nflags, st);
-        if (e == hipSuccess) e = hipMemsetAsync(f->info_err, 0x7f, sizeof(int), st);
         if (e == hipSuccess) {
-            k_cov_reference_order<<<(unsigned)(((long)Dq * Dq + 255) / 256), 256, 0, st>>>(s->P, Gc, n, d, f->dp, Dq, dsc, f->p32);
-            switch (n) {
-                case 2: run_cov_sqrtm_sweep<2>(f, Gc, Fc, Lc, Dq, feedc); break;
-                case 3: run_cov_sqrtm_sweep<3>(f, Gc, Fc, Lc, Dq, feedc); break;
-                case 4: run_cov_sqrtm_sweep<4>(f, Gc, Fc, Lc, Dq, feedc); break;
-                default: rc = -1;
-            }
+            k_cov_reference_order<<<(unsigned)(((long)Dq * Dq + 255) / 256), 256, 0, st>>>(s->P, ws.G, n, d, f->dp, Dq, dsc, f->p32);
+            rc = sweep_ws_enqueue(f, ws, st, 1, "pnmol_state_get_cov_sqrtm");  // (lenient: a covariance may be singular)
             hF.resize((size_t)Dq * Dq);
-            e = hipMemcpyAsync(hF.data(), Fc, sizeof(double) * hF.size(), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(&inf, f->info_err, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (rc == 0) e = hipMemcpyAsync(hF.data(), ws.F, sizeof(double) * hF.size(), hipMemcpyDeviceToHost, st);
+            if (rc == 0 && e == hipSuccess) e = hipMemcpyAsync(&inf, ws.info, sizeof(int), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e == hipSuccess) e = hipGetLastError();
         }
     }
-    for (void* p : {(void*)Gc, (void*)Fc, (void*)Lc, (void*)dsc, (void*)feedc})
-        if (p) (void)hipFree(p);
+    sweep_ws_free(&ws);
+    if (dsc) (void)hipFree(dsc);
+    if (rc != 0) return rc;
     if (e != hipSuccess) {
         ctx->err = std::string("pnmol_state_get_cov_sqrtm: ") + hipGetErrorString(e);
         return -2;
     }
-    if (rc != 0) return rc;
-    if (inf == -2) {
-        ctx->err = "pnmol_state_get_cov_sqrtm: a dependency wait timed out";
-        return -2;
-    }
-    if (inf < Dq) {
-        ctx->err = "pnmol_state_get_cov_sqrtm: covariance not positive semi-definite at pivot " + std::to_string(inf);
-        return -3;
-    }
+    if ((rc = sweep_info_result(ctx, inf, Dq, "pnmol_state_get_cov_sqrtm", "covariance not positive semi-definite")) != 0) return rc;
     for (long r = 0; r < D; ++r) std::memcpy(C_DD + r * D, &hF[(size_t)r * Dq], sizeof(double) * D);
     return 0;
 }
@@ -5027,747 +4723,6 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
     if (o.info >= 0) {
         ctx->err = "innovation matrix not positive definite at pivot " + std::to_string(o.info);
         return -3;
-    }
-    return 0;
-}
-
-// the tail of a smoother step: the sweep's info word, one stream synchronisation
-static int smoother_step_wait(pnmol_filter* f, const pnmol_state* filt_k, double dt, pnmol_state* out) {
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    const long Dp = f->Dp;
-    int inf = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&inf, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipGetLastError());
-    out->t = filt_k->t;
-    out->frame_dt = dt;
-    if (inf == -2) {
-        ctx->err = "pnmol_smoother_step: a dependency wait of the sweep timed out";
-        return -2;
-    }
-    if (inf < Dp) {
-        ctx->err = "pnmol_smoother_step: predicted covariance not positive definite at pivot " + std::to_string(inf);
-        return -3;
-    }
-    return 0;
-}
-
-// What a query inside [t_k, t_k + dt] needs, copied out of the step's own buffers (enqueued behind the step, before the next one
-// reuses them): the point-diagonal blocks of Ps_k (out), C_k = G Ps^h (sm_C) and Ps^h_{k+1} (the product k_sm_build formed), the
-// two means, diag K; with keep_full all of C_k.  On failure nothing is left behind and *bridge is NULL.
-static int make_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt, const pnmol_state* out,
-                       const double* tsn, int keep_full, pnmol_bridge** bridge) {
-    static const char* who = "pnmol_smoother_step_bridge";
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    const size_t sq = (size_t)f->Dp * f->Dp;
-    pnmol_bridge* br = new pnmol_bridge();
-    br->f = f, br->t = filt_k->t, br->dt = dt;
-    f->bridges.fetch_add(1);
-    auto fail = [&](int code, const std::string& why) {
-        ctx->err = std::string(who) + ": " + why;
-        (void)hipStreamSynchronize(st);
-        pnmol_bridge_destroy(br);
-        return code;
-    };
-    const size_t slot = pnmol_dense_block_doubles(f->n, f->dp);
-    hipError_t e = hipSuccess;
-    if (!f->dn_slab || f->dn_slab->used == BRIDGE_SLAB_SLOTS) {  // (a full slab now belongs to its bridges alone)
-        BridgeSlab* sl = new BridgeSlab();
-        e = hipMalloc(&sl->base, sizeof(double) * slot * BRIDGE_SLAB_SLOTS);
-        if (e == hipSuccess) f->dn_slab = sl;
-        else delete sl;
-    }
-    if (e == hipSuccess) {
-        br->slab = f->dn_slab;
-        br->blk = br->slab->base + slot * br->slab->used;
-        br->slab->used += 1, br->slab->live += 1;
-        if (keep_full) e = hipMalloc(&br->Cfull, sizeof(double) * sq);
-    }
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? -4 : -2, hipGetErrorString(e));
-    DenseFrames fr{};
-    for (int a = 0; a < f->n; ++a) fr.sl[a] = 1.0, fr.sr[a] = tsn[a];
-    if (pnmol_dense_launch_gather(st, f->n, out->P, f->sm_C, smooth_next->P, out->mean, smooth_next->mean, f->Kg, fr, f->dp,
-                                  br->blk) != 0)
-        return fail(-2, "kernel launch failed");
-    if (keep_full) {
-        e = hipMemcpyAsync(br->Cfull, f->sm_C, sizeof(double) * sq, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return fail(-2, hipGetErrorString(e));
-    }
-    *bridge = br;
-    return 0;
-}
-
-static int smoother_step_impl(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
-                              pnmol_state* out, int keep_full, pnmol_bridge** bridge) {
-    if (bridge) *bridge = nullptr;
-    if (!f || !filt_k || !smooth_next || !out || out == filt_k || out == smooth_next || filt_k->f != f || smooth_next->f != f ||
-        out->f != f || !(dt > 0.0) || f->ds != f->d || f->p32) {
-        if (f) f->ctx->err = "pnmol_smoother_step: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
-        return -1;
-    }
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int rc_ws = ensure_smoother_ws(f);
-    if (rc_ws != 0) return rc_ws;
-    // everything in the Nordsieck frame of dt: ts / tsn move the two inputs there (as k_predict's IwpConsts.ts)
-    SmoothConsts c{};
-    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
-    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
-    for (int a = 0; a < f->n; ++a) {
-        const double sh = nordsieck_scale(f->nu, a, dt);
-        c.ts[a] = (filt_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, filt_k->frame_dt)) / sh;
-        c.tsn[a] = (smooth_next->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, smooth_next->frame_dt)) / sh;
-    }
-    const long Dp = f->Dp;
-    double *mh = f->sm_vec, *dm = f->sm_vec + Dp;
-    int rc = pnmol_smooth_launch_build(st, f->n, filt_k->P, smooth_next->P, filt_k->mean, smooth_next->mean, f->Kg, c, f->d, f->dp,
-                                       f->sm_G, out->P, f->sm_Psh, mh, dm);
-    if (rc != 0) {
-        ctx->err = "pnmol_smoother_step: kernel launch failed";
-        return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(f->sm_flags, 0, sizeof(int) * f->sm_nflags, st));
-    HIPCHK(ctx, hipMemsetAsync(f->sm_info, 0x7f, sizeof(int), st));
-    switch (f->n) {
-        case 2: run_smoother_sweep<2>(f); break;
-        case 3: run_smoother_sweep<3>(f); break;
-        case 4: run_smoother_sweep<4>(f); break;
-    }
-    const double* V = f->sm_F + Dp * Dp;
-    const double* T = f->sm_F + (2 * Dp + NB) * Dp;
-    rc = pnmol_smooth_launch_finish(st, Dp, V, T, f->sm_Psh, mh, dm, f->sm_gain, f->sm_C, out->P, out->mean, out->var);
-    if (rc != 0) {
-        ctx->err = "pnmol_smoother_step: kernel launch failed";
-        return rc;
-    }
-    if (bridge) {
-        rc = make_bridge(f, filt_k, smooth_next, dt, out, c.tsn, keep_full, bridge);
-        if (rc != 0) return rc;
-    }
-    rc = smoother_step_wait(f, filt_k, dt, out);
-    if (rc != 0 && bridge && *bridge) {
-        pnmol_bridge_destroy(*bridge);
-        *bridge = nullptr;
-    }
-    return rc;
-}
-
-int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
-                        pnmol_state* out) {
-    return smoother_step_impl(f, filt_k, smooth_next, dt, out, 0, nullptr);
-}
-
-// ---- dense output between grid times (kernels in pnmol_dense.hip) ----------------------------------------------------------
-int pnmol_smoother_step_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
-                               pnmol_state* out, int keep_full, pnmol_bridge** bridge) {
-    if (!bridge) {
-        if (f) f->ctx->err = "pnmol_smoother_step_bridge: bad argument (null bridge pointer)";
-        return -1;
-    }
-    return smoother_step_impl(f, filt_k, smooth_next, dt, out, keep_full, bridge);
-}
-
-int pnmol_bridge_destroy(pnmol_bridge* b) {
-    if (!b) return -1;
-    b->f->bridges.fetch_sub(1);
-    hipSetDevice(b->f->ctx->device);
-    if (BridgeSlab* sl = b->slab) {
-        sl->live -= 1;
-        if (sl->live == 0) {
-            if (sl == b->f->dn_slab && sl->used < BRIDGE_SLAB_SLOTS) {
-                sl->used = 0;  // (readers and the next writer of a block are on the ctx stream: ordered)
-            } else {
-                if (sl == b->f->dn_slab) b->f->dn_slab = nullptr;
-                (void)hipFree(sl->base);
-                delete sl;
-            }
-        }
-    }
-    if (b->Cfull) (void)hipFree(b->Cfull);
-    delete b;
-    return 0;
-}
-
-int pnmol_bridge_get_interval(const pnmol_bridge* b, double* t, double* dt, int* has_full) {
-    if (!b) return -1;
-    if (t) *t = b->t;
-    if (dt) *dt = b->dt;
-    if (has_full) *has_full = b->Cfull != nullptr;
-    return 0;
-}
-
-namespace {
-
-// (A_th, Q_th): the IWP over the fraction th of a step, in the Nordsieck frame of the whole step (pnmol/base/iwp.py,
-// _partial_interval): entry by entry, every exponent that meets a non-zero entry is >= 0
-void partial_interval(const pnmol_filter* f, double th, double* A, double* Q) {
-    for (int a = 0; a < f->n; ++a)
-        for (int b = 0; b < f->n; ++b) {
-            A[a * MAXN + b] = b >= a ? f->iwp.A1[a * MAXN + b] * std::pow(th, b - a) : 0.0;
-            Q[a * MAXN + b] = f->iwp.Q1[a * MAXN + b] * std::pow(th, 2 * f->nu + 1 - a - b);
-        }
-}
-
-// pnmol/base/iwp.py, bridge_coefficients: Bp = Q_th A_c^T Q1^-1, M = I - Bp A_c, Bm = M A_th, Qb = M Q_th M^T + Bp Q_c Bp^T
-void bridge_coefficients(const pnmol_filter* f, double th, double* Bm, double* Bp, double* Qb) {
-    const int n = f->n;
-    double A[MAXN * MAXN], Q[MAXN * MAXN], Ac[MAXN * MAXN], Qc[MAXN * MAXN], L[MAXN * MAXN] = {0}, M[MAXN * MAXN];
-    partial_interval(f, th, A, Q);
-    partial_interval(f, 1.0 - th, Ac, Qc);
-    for (int a = 0; a < n; ++a)  // chol(Q1): n x n, positive definite (cond <= 1.6e4 at n = 4)
-        for (int b = 0; b <= a; ++b) {
-            double v = f->iwp.Q1[a * MAXN + b];
-            for (int e = 0; e < b; ++e) v -= L[a * MAXN + e] * L[b * MAXN + e];
-            L[a * MAXN + b] = (a == b) ? std::sqrt(v) : v / L[b * MAXN + b];
-        }
-    for (int col = 0; col < n; ++col) {  // column col of X = Q1^-1 (A_c Q_th); Bp = X^T
-        double y[MAXN];
-        for (int a = 0; a < n; ++a) {
-            double v = 0.0;
-            for (int e = 0; e < n; ++e) v += Ac[a * MAXN + e] * Q[e * MAXN + col];
-            y[a] = v;
-        }
-        for (int a = 0; a < n; ++a) {
-            for (int e = 0; e < a; ++e) y[a] -= L[a * MAXN + e] * y[e];
-            y[a] /= L[a * MAXN + a];
-        }
-        for (int a = n - 1; a >= 0; --a) {
-            for (int e = a + 1; e < n; ++e) y[a] -= L[e * MAXN + a] * y[e];
-            y[a] /= L[a * MAXN + a];
-        }
-        for (int a = 0; a < n; ++a) Bp[col * MAXN + a] = y[a];
-    }
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) {
-            double v = a == b ? 1.0 : 0.0;
-            for (int e = 0; e < n; ++e) v -= Bp[a * MAXN + e] * Ac[e * MAXN + b];
-            M[a * MAXN + b] = v;
-        }
-    double MQ[MAXN * MAXN], BQ[MAXN * MAXN];
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) {
-            double v = 0.0, w = 0.0, u = 0.0;
-            for (int e = 0; e < n; ++e) {
-                v += M[a * MAXN + e] * A[e * MAXN + b];
-                w += M[a * MAXN + e] * Q[e * MAXN + b];
-                u += Bp[a * MAXN + e] * Qc[e * MAXN + b];
-            }
-            Bm[a * MAXN + b] = v, MQ[a * MAXN + b] = w, BQ[a * MAXN + b] = u;
-        }
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b <= a; ++b) {
-            double v = 0.0;
-            for (int e = 0; e < n; ++e) v += MQ[a * MAXN + e] * M[b * MAXN + e] + BQ[a * MAXN + e] * Bp[b * MAXN + e];
-            Qb[a * MAXN + b] = Qb[b * MAXN + a] = v;
-        }
-}
-
-int ensure_dense_scratch(pnmol_filter* f, size_t bytes, const char* who) {
-    if (bytes <= f->dn_cap) return 0;
-    if (f->dn_scratch) (void)hipFree(f->dn_scratch);
-    f->dn_scratch = nullptr, f->dn_cap = 0;
-    const hipError_t e = hipMalloc(&f->dn_scratch, bytes);
-    if (e != hipSuccess) {
-        f->ctx->err = std::string(who) + ": " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? -4 : -2;
-    }
-    f->dn_cap = bytes;
-    return 0;
-}
-
-inline bool times_agree(double a, double b, double dt) {  // the rule of pnmol_samples_step_back
-    return std::fabs(a - b) <= 16.0 * 2.220446049250313e-16 * std::max({std::fabs(a), std::fabs(b), std::fabs(dt)});
-}
-
-// table -> device, one launch, the read-out: means / stds (nq, n, d)
-int run_dense_eval(pnmol_filter* f, const double* blk_dev, bool blk_in_scratch, const std::vector<DenseQuery>& table, int one_sided,
-                   double* means, double* stds, const char* who) {
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    const size_t nq = table.size(), no = nq * (size_t)f->n * f->d;
-    const size_t blk_bytes = blk_in_scratch ? sizeof(double) * pnmol_dense_block_doubles(f->n, f->dp) : 0;
-    char* base = static_cast<char*>(f->dn_scratch);
-    double* out_dev = reinterpret_cast<double*>(base + blk_bytes);
-    DenseQuery* tab_dev = reinterpret_cast<DenseQuery*>(base + blk_bytes + 2 * no * sizeof(double));
-    HIPCHK(ctx, hipMemcpyAsync(tab_dev, table.data(), sizeof(DenseQuery) * nq, hipMemcpyHostToDevice, st));
-    if (pnmol_dense_launch_eval(st, f->n, f->d, f->dp, (int)nq, blk_dev, tab_dev, one_sided, out_dev, out_dev + no) != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return -2;
-    }
-    // straight into the caller's arrays (no host staging: at 10 000 queries the read-out is 123 MB), one synchronisation
-    if (means) HIPCHK(ctx, hipMemcpyAsync(means, out_dev, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (stds) HIPCHK(ctx, hipMemcpyAsync(stds, out_dev + no, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-}
-
-}  // namespace
-
-int pnmol_bridge_eval(const pnmol_bridge* b, int nq, const double* t_q, double* means_qnd, double* stds_qnd) {
-    static const char* who = "pnmol_bridge_eval";
-    if (!b || nq < 1 || !t_q || (!means_qnd && !stds_qnd)) {
-        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, nq < 1)";
-        return -1;
-    }
-    pnmol_filter* f = b->f;
-    pnmol_ctx* ctx = f->ctx;
-    std::vector<DenseQuery> table((size_t)nq);
-    for (int q = 0; q < nq; ++q) {
-        const double t = t_q[q];
-        const bool at_l = times_agree(t, b->t, b->dt), at_r = times_agree(t, b->t + b->dt, b->dt);
-        if (!std::isfinite(t) || (!at_l && !at_r && !(t > b->t && t < b->t + b->dt))) {
-            ctx->err = std::string(who) + ": query time " + std::to_string(t) + " is not inside the bridge's interval [" +
-                       std::to_string(b->t) + ", " + std::to_string(b->t + b->dt) + "]";
-            return -1;
-        }
-        DenseQuery& e = table[(size_t)q];
-        std::memset(&e, 0, sizeof(e));
-        for (int a = 0; a < f->n; ++a) e.sc[a] = nordsieck_scale(f->nu, a, b->dt);
-        const double th = (t - b->t) / b->dt;
-        e.knot = (at_l || !(th > 0.0)) ? 1 : ((at_r || !(th < 1.0)) ? 2 : 0);
-        if (e.knot == 0) {
-            double Qb[MAXN * MAXN];
-            bridge_coefficients(f, th, e.Bm, e.Bp, Qb);
-            for (int a = 0; a < f->n; ++a) e.qbd[a] = Qb[a * MAXN + a];
-        }
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t no = (size_t)nq * f->n * f->d;
-    int rc = ensure_dense_scratch(f, 2 * no * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
-    if (rc != 0) return rc;
-    return run_dense_eval(f, b->blk, false, table, 0, means_qnd, stds_qnd, who);
-}
-
-int pnmol_state_predict(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_state* out) {
-    if (!f || !in || !out || in == out || in->f != f || out->f != f || !(dt > 0.0) || !std::isfinite(dt) || f->ds != f->d || f->p32) {
-        if (f) f->ctx->err = "pnmol_state_predict: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
-        return -1;
-    }
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    SmoothConsts c{};
-    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
-    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
-    for (int a = 0; a < f->n; ++a)
-        c.ts[a] = (in->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, in->frame_dt)) / nordsieck_scale(f->nu, a, dt);
-    if (pnmol_dense_launch_predict(ctx->stream, f->n, in->P, in->mean, f->Kg, c, f->dp, out->P, out->var, out->mean) != 0) {
-        ctx->err = "pnmol_state_predict: kernel launch failed";
-        return -2;
-    }
-    out->t = in->t + dt;
-    out->frame_dt = dt;
-    return 0;
-}
-
-int pnmol_state_predict_marginals(pnmol_filter* f, const pnmol_state* in, int nq, const double* dt_q, double* means_qnd,
-                                  double* stds_qnd) {
-    static const char* who = "pnmol_state_predict_marginals";
-    if (!f || !in || in->f != f || nq < 1 || !dt_q || (!means_qnd && !stds_qnd) || f->ds != f->d || f->p32) {
-        if (f) f->ctx->err = std::string(who) + ": bad argument (null, foreign state, nq < 1, latent-force or fp32 filter)";
-        return -1;
-    }
-    pnmol_ctx* ctx = f->ctx;
-    std::vector<DenseQuery> table((size_t)nq);
-    double sin[MAXN];
-    for (int a = 0; a < f->n; ++a) sin[a] = in->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, in->frame_dt);
-    for (int q = 0; q < nq; ++q) {
-        const double dt = dt_q[q];
-        if (!std::isfinite(dt) || dt < 0.0) {
-            ctx->err = std::string(who) + ": dt_q[" + std::to_string(q) + "] = " + std::to_string(dt) + " is negative or not finite";
-            return -1;
-        }
-        DenseQuery& e = table[(size_t)q];
-        std::memset(&e, 0, sizeof(e));
-        if (dt == 0.0) {  // the state itself
-            e.knot = 1;
-            for (int a = 0; a < f->n; ++a) e.sc[a] = sin[a];
-            continue;
-        }
-        // frame of dt: x_t ~ N(A1 (ts o m), A1 (ts ts^T o P) A1^T + Q1 (x) K), ts = frame change of the input
-        for (int a = 0; a < f->n; ++a) {
-            e.sc[a] = nordsieck_scale(f->nu, a, dt);
-            e.qbd[a] = f->iwp.Q1[a * MAXN + a];
-            for (int b2 = 0; b2 < f->n; ++b2) e.Bm[a * MAXN + b2] = f->iwp.A1[a * MAXN + b2] * (sin[b2] / nordsieck_scale(f->nu, b2, dt));
-        }
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t no = (size_t)nq * f->n * f->d, nb = pnmol_dense_block_doubles(f->n, f->dp);
-    int rc = ensure_dense_scratch(f, (nb + 2 * no) * sizeof(double) + sizeof(DenseQuery) * (size_t)nq, who);
-    if (rc != 0) return rc;
-    double* blk = static_cast<double*>(f->dn_scratch);
-    DenseFrames fr{};
-    for (int a = 0; a < f->n; ++a) fr.sl[a] = fr.sr[a] = 1.0;  // (the block stays in the state's frame; Bm carries the change)
-    if (pnmol_dense_launch_gather(ctx->stream, f->n, in->P, nullptr, nullptr, in->mean, nullptr, f->Kg, fr, f->dp, blk) != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return -2;
-    }
-    return run_dense_eval(f, blk, true, table, 1, means_qnd, stds_qnd, who);
-}
-
-int pnmol_bridge_state(const pnmol_bridge* b, const pnmol_state* smooth_k, const pnmol_state* smooth_next, double t,
-                       pnmol_state* out) {
-    static const char* who = "pnmol_bridge_state";
-    if (!b || !smooth_k || !smooth_next || !out || out == smooth_k || out == smooth_next || smooth_k->f != b->f ||
-        smooth_next->f != b->f || out->f != b->f) {
-        if (b) b->f->ctx->err = std::string(who) + ": bad argument (null, aliasing, state of another filter)";
-        return -1;
-    }
-    pnmol_filter* f = b->f;
-    pnmol_ctx* ctx = f->ctx;
-    if (!b->Cfull) {
-        ctx->err = std::string(who) + ": this bridge was made without keep_full (no cross-covariance C_k)";
-        return -1;
-    }
-    if (!times_agree(smooth_k->t, b->t, b->dt) || !times_agree(smooth_next->t, b->t + b->dt, b->dt)) {
-        ctx->err = std::string(who) + ": the states sit at t = " + std::to_string(smooth_k->t) + " and " +
-                   std::to_string(smooth_next->t) + ", not at the two ends of the bridge's interval";
-        return -1;
-    }
-    const double th = (t - b->t) / b->dt;
-    if (!std::isfinite(t) || !(th > 0.0) || !(th < 1.0)) {
-        ctx->err = std::string(who) + ": t = " + std::to_string(t) + " is not strictly inside the bridge's interval (at its ends "
-                   "the posterior is the state given)";
-        return -1;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DenseMix c{};
-    bridge_coefficients(f, th, c.Bm, c.Bp, c.Qb);
-    for (int a = 0; a < f->n; ++a)
-        for (int e = 0; e < f->n; ++e) {
-            const double sh = nordsieck_scale(f->nu, e, b->dt);
-            c.BmS[a * MAXN + e] = c.Bm[a * MAXN + e] * ((smooth_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, e, smooth_k->frame_dt)) / sh);
-            c.BpS[a * MAXN + e] = c.Bp[a * MAXN + e] * ((smooth_next->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, e, smooth_next->frame_dt)) / sh);
-        }
-    const double* ml = b->blk + 3 * (size_t)f->n * f->n * f->dp;
-    if (pnmol_dense_launch_state(ctx->stream, f->n, smooth_k->P, smooth_next->P, b->Cfull, f->Kg, ml, ml + (size_t)f->n * f->dp, c,
-                                 f->dp, out->P, out->var, out->mean) != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return -2;
-    }
-    out->t = t;
-    out->frame_dt = b->dt;
-    return 0;
-}
-
-// ---- joint posterior draws ---------------------------------------------------------------------------------------------
-int pnmol_samples_create(pnmol_filter* f, int num_samples, pnmol_samples** out) {
-    if (out) *out = nullptr;
-    if (!f || !out || num_samples < 1 || f->ds != f->d || f->p32) {
-        if (f) f->ctx->err = "pnmol_samples_create: bad argument (null, num_samples < 1, latent-force or fp32 filter)";
-        return -1;
-    }
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    pnmol_samples* x = new pnmol_samples();
-    x->f = f;
-    x->S = num_samples;
-    x->Sp = round_up(num_samples, 64);
-    f->samples.fetch_add(1);
-    const size_t blk = sizeof(double) * (size_t)f->Dp * x->Sp;
-    const size_t D = (size_t)f->n * f->d;
-    hipError_t e = hipMalloc(&x->X, blk);
-    if (e == hipSuccess) e = hipMalloc(&x->Xi, 2 * blk);
-    if (e == hipSuccess) e = hipMalloc(&x->Xt, blk);
-    if (e == hipSuccess) e = hipMalloc(&x->R, blk);
-    if (e == hipSuccess) e = hipMalloc(&x->Y, blk);
-    if (e == hipSuccess) e = hipMalloc(&x->stage, sizeof(double) * (size_t)x->S * 2 * D);
-    // (on the ctx stream, like pnmol_state_create; the padding rows and columns of the noise are never written again)
-    if (e == hipSuccess) e = hipMemsetAsync(x->X, 0, blk, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->Xi, 0, 2 * blk, ctx->stream);
-    if (e != hipSuccess) {
-        ctx->err = std::string("pnmol_samples_create: ") + hipGetErrorString(e);
-        pnmol_samples_destroy(x);
-        return e == hipErrorOutOfMemory ? -4 : -2;
-    }
-    *out = x;
-    return 0;
-}
-
-int pnmol_samples_destroy(pnmol_samples* x) {
-    if (!x) return -1;
-    x->f->samples.fetch_sub(1);
-    hipSetDevice(x->f->ctx->device);
-    for (void* p : {(void*)x->X, (void*)x->Xi, (void*)x->Xt, (void*)x->R, (void*)x->Y, (void*)x->stage})
-        if (p) (void)hipFree(p);
-    delete x;
-    return 0;
-}
-
-// the info word(s) of the call's sweep(s): one stream synchronisation
-static int finish_sampler_call(pnmol_filter* f, bool main_sweep, const char* who) {
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    const long Dp = f->Dp;
-    int inf_c = 0, inf_m = 0x7f7f7f7f;
-    HIPCHK(ctx, hipMemcpyAsync(&inf_c, f->sp_info, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (main_sweep) HIPCHK(ctx, hipMemcpyAsync(&inf_m, f->sm_info, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipGetLastError());
-    if (inf_c == -2 || inf_m == -2) {
-        ctx->err = std::string(who) + ": a dependency wait of the sweep timed out";
-        return -2;
-    }
-    if (inf_c < Dp) {
-        ctx->err = std::string(who) + ": covariance not positive semi-definite (NaN?) at pivot " + std::to_string(inf_c);
-        return -3;
-    }
-    if (inf_m < Dp) {
-        ctx->err = std::string(who) + ": predicted covariance not positive definite at pivot " + std::to_string(inf_m);
-        return -3;
-    }
-    return 0;
-}
-
-int pnmol_samples_draw(pnmol_samples* x, const pnmol_state* s, const double* xi_SD, unsigned long long seed,
-                       unsigned long long step_index, double scale) {
-    static const char* who = "pnmol_samples_draw";
-    if (!x || !s || s->f != x->f || !std::isfinite(scale)) {
-        if (x) x->f->ctx->err = std::string(who) + ": bad argument (null, state of another filter, non-finite scale)";
-        return -1;
-    }
-    pnmol_filter* f = x->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    int rc = ensure_sampler_ws(f, who);
-    if (rc != 0) return rc;
-    x->drawn = false;
-    const long Dp = f->Dp;
-    SampleConsts c{};
-    for (int a = 0; a < f->n; ++a) c.ts[a] = 1.0;  // the draw stays in the state's own frame
-    rc = pnmol_sample_launch_build(st, f->n, s->P, s->mean, f->Kg, c, f->d, f->dp, f->sp_Gc, nullptr, f->sp_mh);
-    if (rc != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return rc;
-    }
-    if ((rc = enqueue_sampler_factor(f, who)) != 0) return rc;
-    if ((rc = fill_noise(x, xi_SD, f->n * f->d, seed, step_index, who)) != 0) return rc;
-    // x = m + scale C xi
-    rc = pnmol_sample_launch_thin(st, f->sp_F, x->Xi, x->X, nullptr, f->sp_mh, scale, Dp, x->Sp, 0, 1, 1, f->n);
-    if (rc != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return rc;
-    }
-    if ((rc = finish_sampler_call(f, false, who)) != 0) return rc;
-    x->t = s->t, x->frame_dt = s->frame_dt, x->drawn = true;
-    return 0;
-}
-
-int pnmol_samples_step_back(pnmol_samples* x, const pnmol_state* filt_k, double dt, const double* xi_S2D,
-                            unsigned long long seed, unsigned long long step_index, double scale) {
-    static const char* who = "pnmol_samples_step_back";
-    if (!x || !filt_k || filt_k->f != x->f || !(dt > 0.0) || !std::isfinite(dt) || !std::isfinite(scale) || !x->drawn) {
-        if (x)
-            x->f->ctx->err = std::string(who) + ": bad argument (null, state of another filter, dt <= 0, non-finite scale, or a "
-                                                "block that holds no draw yet)";
-        return -1;
-    }
-    pnmol_filter* f = x->f;
-    pnmol_ctx* ctx = f->ctx;
-    {
-        const double tn = filt_k->t + dt;
-        const double tol = 16.0 * 2.220446049250313e-16 * std::max({std::fabs(tn), std::fabs(x->t), dt});
-        if (!(std::fabs(tn - x->t) <= tol)) {
-            ctx->err = std::string(who) + ": the block holds draws at t = " + std::to_string(x->t) + ", not at filt_k->t + dt = " +
-                       std::to_string(tn) + " (steps out of order?)";
-            return -1;
-        }
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    int rc = ensure_sampler_ws(f, who);
-    if (rc == 0) rc = ensure_smoother_ws(f);
-    if (rc != 0) return rc;
-    const long Dp = f->Dp;
-    const int Sp = x->Sp;
-    SampleConsts c{};
-    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
-    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
-    for (int a = 0; a < f->n; ++a) {  // chol(Q1): n x n, positive definite
-        for (int b = 0; b <= a; ++b) {
-            double v = c.Q1[a * SM_MAXN + b];
-            for (int e = 0; e < b; ++e) v -= c.Lq[a * SM_MAXN + e] * c.Lq[b * SM_MAXN + e];
-            c.Lq[a * SM_MAXN + b] = (a == b) ? std::sqrt(v) : v / c.Lq[b * SM_MAXN + b];
-        }
-        const double sh = nordsieck_scale(f->nu, a, dt);
-        c.ts[a] = (filt_k->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, filt_k->frame_dt)) / sh;
-        c.tsn[a] = (x->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, x->frame_dt)) / sh;
-    }
-    auto failed = [&](int code) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        x->drawn = false;  // the block may be half written
-        if (f->sp_stream) (void)hipStreamSynchronize(f->sp_stream);  // (nothing of this call may outlive it)
-        return code;
-    };
-    // C_k sweep -> xt, r -> main sweep -> V (T^T r)
-    rc = pnmol_sample_launch_build(st, f->n, filt_k->P, filt_k->mean, f->Kg, c, f->d, f->dp, f->sp_Gc, f->sm_G, f->sp_mh);
-    if (rc != 0) return failed(rc);
-    // The main sweep needs nothing of what follows on the ctx stream before `T^T r`.  Where both sweeps are the left-looking
-    // kernel (more than 17 column blocks; its workgroups wait for earlier-dispatched ones of their own launch only, so two
-    // launches in flight cannot block each other) it runs beside the factorisation of P^h; the register-resident kernel of
-    // the small problems wants its workgroups co-resident and stays in line.
-    const bool beside = Dp / NB > 17 || !sweep_rl_enabled();
-    hipStream_t sw = beside ? f->sp_stream : st;
-    auto main_sweep = [&]() -> int {
-        HIPCHK(ctx, hipMemsetAsync(f->sm_flags, 0, sizeof(int) * f->sm_nflags, sw));
-        HIPCHK(ctx, hipMemsetAsync(f->sm_info, 0x7f, sizeof(int), sw));
-        switch (f->n) {
-            case 2: run_smoother_sweep<2>(f, sw); break;
-            case 3: run_smoother_sweep<3>(f, sw); break;
-            case 4: run_smoother_sweep<4>(f, sw); break;
-        }
-        return 0;
-    };
-    if (beside) {
-        HIPCHK(ctx, hipEventRecord(f->sp_ev_built, st));
-        HIPCHK(ctx, hipStreamWaitEvent(sw, f->sp_ev_built, 0));
-        if ((rc = main_sweep()) != 0) return rc;
-        HIPCHK(ctx, hipEventRecord(f->sp_ev_swept, sw));
-    }
-    if ((rc = enqueue_sampler_factor(f, who)) != 0) return rc;
-    if ((rc = fill_noise(x, xi_S2D, 2 * f->n * f->d, seed, step_index, who)) != 0) return rc;
-    rc = pnmol_sample_launch_thin(st, f->sp_F, x->Xi, x->Xt, nullptr, f->sp_mh, scale, Dp, Sp, 0, 1, 1, f->n);  // xt = m^h + s C xi_1
-    if (rc == 0) rc = pnmol_sample_launch_thin(st, f->sp_Gamma, x->Xi + Dp * Sp, x->R, nullptr, nullptr, 1.0, f->dp, Sp, 0, 1, f->n, 0);
-    if (rc == 0) rc = pnmol_sample_launch_resid(st, f->n, c, scale, f->dp, Sp, x->X, x->Xt, x->R, x->Y);
-    if (rc != 0) return failed(rc);
-    if (beside) HIPCHK(ctx, hipStreamWaitEvent(st, f->sp_ev_swept, 0));
-    else if ((rc = main_sweep()) != 0) return rc;
-    const double* V = f->sm_F + Dp * Dp;
-    const double* T = f->sm_F + (2 * Dp + NB) * Dp;
-    rc = pnmol_sample_launch_thin(st, T, x->Y, x->R, nullptr, nullptr, 1.0, Dp, Sp, 1, 1, 1, 0);        // y = T^T r = L^-1 r
-    if (rc == 0) rc = pnmol_sample_launch_thin(st, V, x->R, x->X, x->Xt, nullptr, 1.0, Dp, Sp, 0, 0, 1, 0);  // x = xt + V y
-    if (rc != 0) return failed(rc);
-    x->drawn = false;
-    if ((rc = finish_sampler_call(f, true, who)) != 0) return rc;
-    x->t = filt_k->t, x->frame_dt = dt, x->drawn = true;
-    return 0;
-}
-
-int pnmol_samples_clone(const pnmol_samples* x, pnmol_samples** out) {
-    if (out) *out = nullptr;
-    if (!x || !out) return -1;
-    int rc = pnmol_samples_create(x->f, x->S, out);
-    if (rc != 0) return rc;
-    pnmol_ctx* ctx = x->f->ctx;
-    pnmol_samples* o = *out;
-    HIPCHK(ctx, hipMemcpyAsync(o->X, x->X, sizeof(double) * (size_t)x->f->Dp * x->Sp, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    o->t = x->t, o->frame_dt = x->frame_dt, o->drawn = x->drawn;
-    return 0;
-}
-
-int pnmol_samples_interpolate(pnmol_samples* out, const pnmol_samples* left, const pnmol_samples* right, double t,
-                              const double* xi_SD, unsigned long long seed, unsigned long long step_index, double scale) {
-    static const char* who = "pnmol_samples_interpolate";
-    if (!out || !left || out == left || out == right || left->f != out->f || (right && right->f != out->f) || left->S != out->S ||
-        (right && right->S != out->S) || !left->drawn || (right && !right->drawn) || !std::isfinite(scale) || !std::isfinite(t) ||
-        !(t > left->t) || (right && !(t < right->t))) {
-        if (out)
-            out->f->ctx->err = std::string(who) + ": bad argument (null, aliasing blocks, blocks of another filter or size, a block "
-                                                  "that holds no draw, non-finite scale, or t not strictly between the blocks' times)";
-        return -1;
-    }
-    pnmol_filter* f = out->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    int rc = ensure_sampler_ws(f, who);
-    if (rc != 0) return rc;
-    // frame of h = t_r - t_l (two-sided) or of h = t - t_l (one-sided: the prior carried forwards, B+ = 0, Qb = Q1)
-    const double h = (right ? right->t : t) - left->t;
-    DenseDrawMix c{};
-    double Bm[MAXN * MAXN] = {0}, Bp[MAXN * MAXN] = {0}, Qb[MAXN * MAXN] = {0};
-    if (right) {
-        bridge_coefficients(f, (t - left->t) / h, Bm, Bp, Qb);
-    } else {
-        std::memcpy(Bm, f->iwp.A1, sizeof(Bm));
-        std::memcpy(Qb, f->iwp.Q1, sizeof(Qb));
-    }
-    for (int a = 0; a < f->n; ++a) {  // chol(Qb), positive semi-definite: a pivot that is not positive gives a zero column
-        for (int b = 0; b <= a; ++b) {
-            double v = Qb[a * MAXN + b];
-            for (int e = 0; e < b; ++e) v -= c.Ls[a * MAXN + e] * c.Ls[b * MAXN + e];
-            if (a == b) c.Ls[a * MAXN + a] = v > 0.0 ? std::sqrt(v) : 0.0;
-            else c.Ls[a * MAXN + b] = c.Ls[b * MAXN + b] > 0.0 ? v / c.Ls[b * MAXN + b] : 0.0;
-        }
-    }
-    for (int a = 0; a < f->n; ++a)
-        for (int b = 0; b < f->n; ++b) {
-            const double sh = nordsieck_scale(f->nu, b, h);
-            c.BmS[a * MAXN + b] = Bm[a * MAXN + b] * ((left->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, b, left->frame_dt)) / sh);
-            if (right) c.BpS[a * MAXN + b] = Bp[a * MAXN + b] * ((right->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, b, right->frame_dt)) / sh);
-            c.Ls[a * MAXN + b] *= scale;
-        }
-    out->drawn = false;
-    const long Dp = f->Dp;
-    const int Sp = out->Sp, D = f->n * f->d;
-    double* Xi2 = out->Xi + Dp * Sp;  // derivative-major noise rows (the xi_2 half of the block's noise buffer)
-    if (xi_SD) {
-        HIPCHK(ctx, hipMemcpyAsync(out->stage, xi_SD, sizeof(double) * (size_t)out->S * D, hipMemcpyHostToDevice, st));
-        rc = pnmol_sample_launch_scatter(st, out->stage, out->S, D, f->d, f->dp, 0, Sp, Xi2);
-    } else {
-        rc = pnmol_sample_launch_noise(st, seed, step_index, out->S, D, f->d, f->dp, 0, Sp, Xi2, nullptr);
-    }
-    if (rc == 0) rc = pnmol_sample_launch_thin(st, f->sp_Gamma, Xi2, out->R, nullptr, nullptr, 1.0, f->dp, Sp, 0, 1, f->n, 0);
-    if (rc == 0) rc = pnmol_dense_launch_draw_mix(st, f->n, c, f->dp, Sp, left->X, right ? right->X : nullptr, out->R, out->X);
-    if (rc != 0) {
-        ctx->err = std::string(who) + ": kernel launch failed";
-        return rc;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipGetLastError());
-    out->t = t, out->frame_dt = h, out->drawn = true;
-    return 0;
-}
-
-int pnmol_samples_get(const pnmol_samples* x, double* x_Snd) {
-    if (!x || !x_Snd || !x->drawn) {
-        if (x) x->f->ctx->err = "pnmol_samples_get: bad argument (null, or a block that holds no draw)";
-        return -1;
-    }
-    pnmol_filter* f = x->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    double sc[MAXN];
-    for (int a = 0; a < f->n; ++a) sc[a] = x->frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, x->frame_dt);
-    if (pnmol_sample_launch_get(ctx->stream, f->n, f->d, f->dp, x->Sp, x->S, sc, x->X, x->stage) != 0) {
-        ctx->err = "pnmol_samples_get: kernel launch failed";
-        return -2;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(x_Snd, x->stage, sizeof(double) * (size_t)x->S * f->n * f->d, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int pnmol_samples_get_time(const pnmol_samples* x, double* t) {
-    if (!x || !t || !x->drawn) return -1;
-    *t = x->t;
-    return 0;
-}
-
-int pnmol_sample_noise(pnmol_ctx* ctx, unsigned long long seed, unsigned long long step_index, int rows, int cols, double* out) {
-    if (!ctx || !out || rows < 1 || cols < 1) {
-        if (ctx) ctx->err = "pnmol_sample_noise: bad argument";
-        return -1;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    double* dev = nullptr;
-    const size_t bytes = sizeof(double) * (size_t)rows * cols;
-    hipError_t e = hipMalloc(&dev, bytes);
-    if (e != hipSuccess) {
-        ctx->err = std::string("pnmol_sample_noise: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? -4 : -2;
-    }
-    int rc = pnmol_sample_launch_noise(ctx->stream, seed, step_index, rows, cols, 1, 1, 1, 0, nullptr, dev);
-    if (rc == 0) e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (rc == 0 && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dev);
-    if (rc != 0 || e != hipSuccess) {
-        ctx->err = std::string("pnmol_sample_noise: ") + (rc != 0 ? "kernel launch failed" : hipGetErrorString(e));
-        return -2;
     }
     return 0;
 }

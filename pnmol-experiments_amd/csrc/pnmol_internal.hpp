@@ -2,8 +2,42 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <string>
+#include <vector>
+
+#include "pnmol_hip.h"
+
+constexpr int NB = 32;    // factorisation block
+constexpr int MAXN = 4;   // max derivatives + 1
+
+namespace {
+// (unnamed on purpose: kernels of pnmol_hip.hip take it by value and their symbol names spell the namespace)
+struct IwpConsts {
+    double A1[MAXN * MAXN];  // flip(pascal_lower)  base/iwp.py:24-27
+    double Q1[MAXN * MAXN];  // flip(hilbert)       base/iwp.py:29
+    double ts[MAXN];         // frame change  s_old[a] / s_new[a]
+};
+}  // namespace
+
+#define HIPCHK(ctx, call)                                                                        \
+    do {                                                                                         \
+        hipError_t e__ = (call);                                                                 \
+        if (e__ != hipSuccess) {                                                                 \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
+            return -2;                                                                           \
+        }                                                                                        \
+    } while (0)
+
+inline int round_up(int x, int q) { return (x + q - 1) / q * q; }
+
+inline double nordsieck_scale(int nu, int a, double dt) {  // base/iwp.py:55-62
+    double fact = 1.0;
+    for (int q = 2; q <= nu - a; ++q) fact *= q;
+    return std::pow(std::fabs(dt), nu - a + 0.5) / fact;
+}
 
 struct pnmol_ctx {
     int device = 0;
@@ -14,7 +48,193 @@ struct pnmol_ctx {
     std::atomic<int> children{0};
 };
 
-// The RTS smoother step (pnmol_smoother_step; kernels in pnmol_smooth.hip, host side and sweep in pnmol_hip.hip).
+// Workspace of one tile sweep (launch_sweep, pnmol_hip.hip) outside the filter step: the matrix G (rt x cb tiles of NB x NB,
+// leading dimension ld = cb NB) that the caller fills, the result F of the same shape, the L_jj^-1 tiles, the feed tiles of
+// the register-resident kernel, the dependency flags and the info word.
+struct SweepWs {
+    double *G = nullptr, *F = nullptr, *Linv = nullptr, *feed = nullptr;
+    int *flags = nullptr, *info = nullptr;
+    int nflags = 0;
+    int rt = 0, cb = 0, ld = 0;
+    bool left_looking = false;  // this shape runs k_sweep (more than 17 column blocks, or PNMOL_HIP_SWEEP_RL=0), not k_sweep_rl
+};
+// Allocate for a shape; F and Linv are zeroed on the ctx stream (the sweep never writes all of them).  A tall shape (rt > cb)
+// has the error model's layout [...; zero block; I]: G is zeroed and its last cb row blocks are set to the identity.
+// On failure nothing is left allocated and the hipError_t is returned.
+hipError_t sweep_ws_alloc(SweepWs* w, pnmol_ctx* ctx, int rt, int cb);
+void sweep_ws_free(SweepWs* w);
+// Zero the flags, reset the info word and launch the sweep of w->G on `st`.  lenient: 0 = a pivot that is not positive is an
+// error, 1 = it is dropped (positive semi-definite input).  -1 (ctx->err names `who`): unsupported number of derivatives.
+int sweep_ws_enqueue(pnmol_filter* f, const SweepWs& w, hipStream_t st, int lenient, const char* who);
+// One reading of a sweep's info word (`limit` = number of pivots): 0, or -2 / -3 with ctx->err = "<who>: <wait>" /
+// "<who>: <what> at pivot k".
+int sweep_info_result(pnmol_ctx* ctx, int inf, long limit, const char* who, const char* what,
+                      const char* wait = "a dependency wait timed out");
+
+struct pnmol_filter {
+    pnmol_ctx* ctx = nullptr;
+    int d = 0, n = 0, nu = 0, nB = 0, m = 0, dp = 0, mp = 0, CB = 0, RBS = 0, RBW = 0, RT = 0, ellw = 0;
+    int* tickets = nullptr;   // device: read-out blocks that have taken their slot (k_readout with the next step's role)
+    int* last_ctr = nullptr;  // device: step-counter value of the last step of the running pnmol_filter_steps call
+    int fuse_predict = 1;     // PNMOL_HIP_FUSE_PREDICT: predict the next step's covariance in the down-date epilogue
+    int* flags = nullptr;  // k_sweep dependency flags: row[RT], diag[CB], abort, claim[CB*CB] (helpers); k_sweep_rl: rl_flags()
+    int nflags = 0;        // words allocated (all of them are zeroed before every sweep)
+    double* hs_scratch = nullptr;  // helpers' partial sums, one tile per (row, target step)
+    int w_gemm = 0;        // ... and W = (P- H^T) Ls^-T as a GEMM behind a sweep without the rows of W (k_w_gemm)
+    int dd_big = 0;        // large problems: sweep alone + k_downdate_big (PNMOL_HIP_DD_BIG=0/1 overrides; see there)
+    int sweep_mode = 2;    // PNMOL_HIP_SWEEP: 2 = k_sweep with the covariance down-date riding along in the same launch,
+                           // 1 = k_sweep, then k_downdate; 0 = k_diag0 + one k_panel launch per panel, then k_downdate
+    int ds = 0;  // spatial components of the state (= d, or 2d for the latent-force model [u; eps])
+    bool counted = false;  // this filter is in live_rl_filters[device]
+    bool registered = false;  // this filter is counted in ctx->children
+    std::atomic<int> states{0};  // live pnmol_state objects of this filter (pnmol_filter_destroy refuses while > 0)
+    int xcd_home = -1;  // k_sweep_rl: >= 0: XCD-local layout (XL), chain workgroup and S row blocks on this XCD; -1: spread layout
+    int p32 = 0;        // pnmol_filter_desc.dtype = 1: covariances (state, predicted, Q) are stored and down-dated in fp32
+    size_t psz = 8;     // bytes per covariance element
+    long Dp = 0;
+    IwpConsts iwp{};
+    int* ell_col = nullptr;
+    double* ell_val = nullptr;
+    // the operator given at creation (pde.L), kept for pnmol_filter_set_operator_diagonal: its ELL image, the slot of the
+    // diagonal entry of every PDE row (-1: the row has none), and a pinned staging buffer [jdiag d | shift mp]
+    int* ell_col_base = nullptr;
+    double* ell_val_base = nullptr;
+    int* ell_diag_slot = nullptr;
+    int base_w = 0, base_has_diag = 0;
+    int ell_is_base = 1;      // ell_col / ell_val hold the base image (diagonal slots aside): no dense upload since the last restore
+    double* h_op = nullptr;
+    double* h_op_dev = nullptr;
+    hipEvent_t ev_op = nullptr;
+    double *Kg = nullptr, *rdiag = nullptr, *Rdense = nullptr, *shift = nullptr;
+    double *G = nullptr, *F = nullptr, *Linv = nullptr, *Ppred = nullptr, *mpred = nullptr, *zbuf = nullptr;
+    double *var = nullptr, *Sqinv = nullptr, *rec = nullptr, *part = nullptr, *sdiag = nullptr;
+    int* info = nullptr;
+    std::vector<double> sqdiag;
+    double* Qfull = nullptr;  // Q1 (x) K as a dense Dp x Dp matrix (on-device error model), allocated on first use
+    int* one = nullptr;       // device constant 1 (step-counter stand-in for sweeps outside the step loop)
+    int* info_err = nullptr;  // info word of those sweeps
+    double sq_dt = -1.0;
+    std::vector<double> hB;   // host copy of pde.B (nB x d) for operator rebuilds
+    int ell_cap = 0;          // allocated ELL width
+    // scratch state for ping-pong inside steps()
+    double *tmpP = nullptr, *tmpMean = nullptr;
+    double *rec_means = nullptr, *rec_stds = nullptr;
+    double* h_pin = nullptr;  // pinned host staging: [rec 4k | means k*d | stds k*d | info k ints]
+    double* h_pin_dev = nullptr;  // the same buffer as the device sees it (mapped)
+    int rec_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float last_ms = 0.f;
+    int* ctr = nullptr;  // device step counter (slot of the per-step outputs)
+    int pending_k = 0;   // steps enqueued by pnmol_filter_steps_begin and not yet collected
+    double pending_dt = 0.0;
+    pnmol_state* pending_state = nullptr;
+    struct GraphEntry {
+        double *P0, *P1, *var;
+        double dt;
+        int nsteps;
+        bool have_sq;
+        bool fused;
+        hipGraphExec_t exec;
+        bool launched;  // the first launch of an executable graph costs ~50 ms of host time (ROCm 7.2)
+    };
+    std::vector<GraphEntry> graphs;
+    int graph_chunk = 10;  // steps per captured graph (even); 0 disables graphs
+    // RTS smoother (pnmol_smoother_step), allocated on first use: the sweep's tall matrices [P-; P A^T; 0; I] -> [L; V; 0; T]
+    // ((3 Dp/32 + 1) * 32 x Dp), its L_jj^-1 tiles, feed tiles and flags, and G, C, Ps^h (Dp x Dp), [m^h | dm] (2 Dp)
+    SweepWs sm_sweep;
+    double *sm_gain = nullptr, *sm_C = nullptr, *sm_Psh = nullptr, *sm_vec = nullptr;
+    // Joint draws (pnmol_samples_*), allocated on first use: the square lenient sweep P^h -> C (sp_Gc, sp_F: Dp x Dp, its
+    // L_jj^-1 tiles, feed tiles, flags, info word), Gamma (dp x dp, from the host copy kept at creation) and m^h (Dp).  The
+    // main sweep of a backward step runs in the smoother's workspace above.
+    SweepWs sp_sweep;
+    double *sp_Gamma = nullptr, *sp_mh = nullptr;
+    // a backward step has two independent sweeps (P^h -> C and [P-; P A^T; 0; I]): on wide problems the second one runs on
+    // this side stream, between the two events, while the ctx stream factorises P^h and forms xt and r
+    hipStream_t sp_stream = nullptr;
+    hipEvent_t sp_ev_built = nullptr, sp_ev_swept = nullptr;
+    std::vector<double> hGamma;        // desc->Gamma padded to dp x dp (white-noise fp64 filters)
+    std::atomic<int> samples{0};       // live pnmol_samples objects of this filter (pnmol_filter_destroy refuses while > 0)
+    // Dense output (pnmol_bridge_*, pnmol_state_predict_marginals): scratch for the query table and the read-out, grown on demand
+    std::atomic<int> bridges{0};       // live pnmol_bridge objects of this filter (pnmol_filter_destroy refuses while > 0)
+    void* dn_scratch = nullptr;
+    size_t dn_cap = 0;
+    struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
+};
+
+struct pnmol_state {
+    pnmol_filter* f = nullptr;
+    double* mean = nullptr;  // Dp
+    double* P = nullptr;     // Dp*Dp
+    double* var = nullptr;   // Dp   marginal variances, same frame as P
+    double t = 0.0;
+    double frame_dt = 0.0;  // 0 = raw coordinates, else Nordsieck frame of that dt
+};
+
+// The blocks of a filter's bridges come out of slabs of BRIDGE_SLAB_SLOTS blocks: smooth() makes one bridge per step, and a device
+// allocation per step is what the bridges would otherwise cost most.  A slab is freed when the last bridge in it is destroyed (the
+// filter's current slab is reused instead while it has free slots).
+constexpr int BRIDGE_SLAB_SLOTS = 64;
+struct BridgeSlab {
+    double* base = nullptr;
+    int used = 0;  // slots handed out
+    int live = 0;  // bridges alive
+};
+
+struct pnmol_bridge {
+    pnmol_filter* f = nullptr;
+    BridgeSlab* slab = nullptr;
+    double* blk = nullptr;    // point-diagonal blocks of Ps_k, C_k, Ps_{k+1}, the two means, diag K (pnmol_dense_block_doubles): a slot of slab
+    double* Cfull = nullptr;  // C_k (Dp x Dp), kept on request
+    double t = 0.0, dt = 0.0; // the interval [t, t + dt]; everything above is in the Nordsieck frame of dt
+};
+
+struct pnmol_samples {
+    pnmol_filter* f = nullptr;
+    int S = 0, Sp = 0;       // draws, padded to a multiple of 64
+    double* X = nullptr;     // Dp x Sp: the draws at time t, in the frame frame_dt
+    double* Xi = nullptr;    // 2 Dp x Sp: noise [xi_1; xi_2]
+    double* Xt = nullptr;    // Dp x Sp: xt = m + s C xi_1
+    double* R = nullptr;     // Dp x Sp: Gamma xi_2 per derivative block, then T^T r
+    double* Y = nullptr;     // Dp x Sp: r
+    double* stage = nullptr; // S x 2D: host-supplied noise / read-out, allocated on first use
+    double t = 0.0, frame_dt = 0.0;
+    bool drawn = false;
+};
+
+// raw-coordinate scale of every derivative in the Nordsieck frame of frame_dt (0 = raw coordinates already)
+inline void frame_scales(const pnmol_filter* f, double frame_dt, double* sc) {
+    for (int a = 0; a < f->n; ++a) sc[a] = frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, frame_dt);
+}
+inline void frame_scales(const pnmol_state* s, double* sc) { frame_scales(s->f, s->frame_dt, sc); }
+// frame change of derivative a from the Nordsieck frame of from_dt (0 = raw coordinates) into that of to_dt
+inline double frame_ratio(const pnmol_filter* f, int a, double from_dt, double to_dt) {
+    return (from_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, from_dt)) / nordsieck_scale(f->nu, a, to_dt);
+}
+// two times are the same grid point (dt: the step they are measured against)
+inline bool times_agree(double a, double b, double dt) {
+    return std::fabs(a - b) <= 16.0 * 2.220446049250313e-16 * std::max({std::fabs(a), std::fabs(b), std::fabs(dt)});
+}
+// lower Cholesky factor of the leading n x n block of A (row pitch MAXN; L zero on entry).  semidefinite: a pivot that is
+// not positive gives a zero column instead of a NaN.
+inline void small_cholesky(int n, const double* A, double* L, bool semidefinite = false) {
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            double v = A[a * MAXN + b];
+            for (int e = 0; e < b; ++e) v -= L[a * MAXN + e] * L[b * MAXN + e];
+            if (!semidefinite) L[a * MAXN + b] = (a == b) ? std::sqrt(v) : v / L[b * MAXN + b];
+            else if (a == b) L[a * MAXN + a] = v > 0.0 ? std::sqrt(v) : 0.0;
+            else L[a * MAXN + b] = L[b * MAXN + b] > 0.0 ? v / L[b * MAXN + b] : 0.0;
+        }
+}
+
+// What each feature hung on the filter (pnmol_filter_destroy)
+void pnmol_smooth_free_ws(pnmol_filter* f);
+void pnmol_sample_free_ws(pnmol_filter* f);
+void pnmol_dense_free_ws(pnmol_filter* f);
+// pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
+int pnmol_smooth_ensure_ws(pnmol_filter* f);
+
+// The RTS smoother step (pnmol_smoother_step; pnmol_smooth.hip).
 constexpr int SM_MAXN = 4;
 struct SmoothConsts {
     double A1[SM_MAXN * SM_MAXN];  // IWP transition in the Nordsieck frame (IwpConsts.A1)
@@ -22,15 +242,8 @@ struct SmoothConsts {
     double ts[SM_MAXN];            // frame change of the filtered state into the frame of h
     double tsn[SM_MAXN];           // frame change of the smoothed successor into the frame of h
 };
-// P^h, P- and P^h A^T into Pout / the sweep's tall matrix Gs, Ps^h into Psh, mh = m^h, dm = ms^h - A m^h
-int pnmol_smooth_launch_build(hipStream_t st, int n, const double* P, const double* Ps, const double* m, const double* ms,
-                              const double* Kg, const SmoothConsts& c, int d, int dp, double* Gs, double* Pout, double* Psh,
-                              double* mh, double* dm);
-// from the sweep's V = P A^T L^-T and T = L^-T: G, C = G Ps^h, Pout = P^h - V V^T + C G^T (mirrored), var, mout = mh + G dm
-int pnmol_smooth_launch_finish(hipStream_t st, long Dp, const double* V, const double* T, const double* Psh, const double* mh,
-                               const double* dm, double* G, double* C, double* Pout, double* mout, double* var);
 
-// Joint posterior draws (pnmol_samples_*; kernels in pnmol_sample.hip, host side in pnmol_hip.hip).  A sample block is
+// Joint posterior draws (pnmol_samples_*; pnmol_sample.hip).  A sample block is
 // Dp x Sp row-major (row = state component, derivative-major like a mean; column = draw, Sp = S rounded up to 64), the
 // noise block 2 Dp x Sp (xi_1 over xi_2), padding zero.
 struct SampleConsts {
@@ -40,28 +253,8 @@ struct SampleConsts {
     double ts[SM_MAXN];            // frame change of the filtered state into the frame of h
     double tsn[SM_MAXN];           // frame change of the sample block into the frame of h
 };
-// Gc = P^h, point-major, with unit pivots on the padded points (input of the lenient sweep), Gs (may be null) = [P-; P^h A^T], mh = m^h
-int pnmol_sample_launch_build(hipStream_t st, int n, const double* P, const double* m, const double* Kg, const SampleConsts& c,
-                              int d, int dp, double* Gc, double* Gs, double* mh);
-// standard normals of (seed, step_index) for `rows` draws x `cols` components: into the noise block Xi (component c < D ->
-// row c, the input of the point-major factor; c >= D -> row Dp + ((c - D) / d) dp + (c - D) % d), or, Xi == null, into dense (rows, cols) row-major.
-// n = 0: every component is placed derivative-major, c -> row (c / d) dp + c % d of Xi (the noise of pnmol_samples_interpolate)
-int pnmol_sample_launch_noise(hipStream_t st, unsigned long long seed, unsigned long long step_index, int rows, int cols, int d,
-                              int dp, int n, int Sp, double* Xi, double* dense);
-// the same placement for host-supplied noise: stage (rows, cols) row-major on the device -> Xi
-int pnmol_sample_launch_scatter(hipStream_t st, const double* stage, int rows, int cols, int d, int dp, int n, int Sp, double* Xi);
-// Y = [add] + [addvec 1^T] + alpha op(M) X for `batch` stacked (rows x Sp) blocks of X / Y (M rows x rows, row-major, the same
-// for every block).  trans: op(M) = M^T; lower: op(M) is lower triangular (what lies above the diagonal is not read);
-// perm_n > 0: the rows of op(M) are point-major (j perm_n + a) and the result is stored derivative-major.
-int pnmol_sample_launch_thin(hipStream_t st, const double* M, const double* X, double* Y, const double* add, const double* addvec,
-                             double alpha, long rows, int Sp, int trans, int lower, int batch, int perm_n);
-// R = tsn x_next - A1 xt - scale Lq W  (n x n mixes of the derivative blocks, elementwise over points and draws)
-int pnmol_sample_launch_resid(hipStream_t st, int n, const SampleConsts& c, double scale, int dp, int Sp, const double* xnext,
-                              const double* xt, const double* W, double* R);
-// out (S, n, d) row-major = sc[a] X[(a dp + j) Sp + i]
-int pnmol_sample_launch_get(hipStream_t st, int n, int d, int dp, int Sp, int S, const double* sc, const double* X, double* out);
 
-// Dense output between grid times (pnmol_bridge_*, pnmol_state_predict*; kernels in pnmol_dense.hip, host side in pnmol_hip.hip).
+// Dense output between grid times (pnmol_bridge_*, pnmol_state_predict*; pnmol_dense.hip).
 // Point-diagonal block of an interval, the storage of a pnmol_bridge: [Pl | Cx | Pr] (each N*N rows of dp: entry (a, b) of the
 // n x n block of the matrix at equal mesh points), [ml | mr] (N rows of dp each), diag K (dp).
 inline size_t pnmol_dense_block_doubles(int n, int dp) { return (size_t)(3 * n * n + 2 * n + 1) * dp; }
@@ -82,19 +275,12 @@ struct DenseQuery {
 struct DenseMix {
     double BmS[SM_MAXN * SM_MAXN], BpS[SM_MAXN * SM_MAXN], Bm[SM_MAXN * SM_MAXN], Bp[SM_MAXN * SM_MAXN], Qb[SM_MAXN * SM_MAXN];
 };
-// blk <- point-diagonal blocks of sl sl^T o Pl, Cx (as it is), sr sr^T o Pr, sl o ml, sr o mr, diag K (Cx / Pr / mr may be null:
-// the one-sided case, their part of blk is left alone)
-int pnmol_dense_launch_gather(hipStream_t st, int n, const double* Pl, const double* Cx, const double* Pr, const double* ml,
-                              const double* mr, const double* Kg, const DenseFrames& c, int dp, double* blk);
-// means / stds (nq, n, d) row-major on the device from blk and the table of nq rows; one_sided: the Bp terms are skipped
-int pnmol_dense_launch_eval(hipStream_t st, int n, int d, int dp, int nq, const double* blk, const DenseQuery* table, int one_sided,
-                            double* means, double* stds);
-// Pout = A1 (ts ts^T o P) A1^T + Q1 (x) K, var = diag, mout = A1 (ts o m)   (c.ts: frame change of the input; c.tsn unused)
-int pnmol_dense_launch_predict(hipStream_t st, int n, const double* P, const double* m, const double* Kg, const SmoothConsts& c,
-                               int dp, double* Pout, double* var, double* mout);
-// Pout = BmS Pl BmS^T + Bm C Bp^T + (Bm C Bp^T)^T + BpS Pr BpS^T + Qb (x) K (both halves, var = diag), mout = Bm ml + Bp mr
-int pnmol_dense_launch_state(hipStream_t st, int n, const double* Pl, const double* Pr, const double* C, const double* Kg,
-                             const double* ml, const double* mr, const DenseMix& c, int dp, double* Pout, double* var, double* mout);
+// pnmol/base/iwp.py, bridge_coefficients, at the fraction th of a step: n x n matrices of row pitch MAXN
+void bridge_coefficients(const pnmol_filter* f, double th, double* Bm, double* Bp, double* Qb);
+// What a query inside [t_k, t_k + dt] needs, copied out of a smoother step's own buffers right behind it (tsn: the frame
+// change of smooth_next).  On failure nothing is left behind and *bridge is NULL.
+int pnmol_dense_make_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                            const pnmol_state* out, const double* tsn, int keep_full, pnmol_bridge** bridge);
 // The draw at t between (or behind) drawn neighbours: out = BmS xl [+ BpS xr] + Ls W on (Dp x Sp) sample blocks, the n x n mixes
 // of the derivative blocks element-wise over points and draws (W = Gamma xi per derivative block; Ls lower triangular, scaled)
 struct DenseDrawMix {

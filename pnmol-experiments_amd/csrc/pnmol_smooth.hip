@@ -1,4 +1,4 @@
-// pnmol_smooth.hip -- kernels of the Rauch-Tung-Striebel backward step (`pnmol_smoother_step`, include/pnmol_hip.h).
+// pnmol_smooth.hip -- the Rauch-Tung-Striebel backward step (`pnmol_smoother_step`, include/pnmol_hip.h): kernels, then host side.
 //
 // Reference: src/pnmol/base/kalman.py:33-46 (smoother_step_traditional), in the Nordsieck frame of the step h that the
 // forward step used.  With P = P_k (filtered), A = A1 (x) I, Q = Q1 (x) K:
@@ -9,6 +9,8 @@
 // every product (k_sm_gemm) and the mirror of the lower-half results with the marginal variances (k_sm_mirror).
 // Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp, row-major, zero padding.
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "pnmol_internal.hpp"
 
@@ -244,11 +246,9 @@ __global__ __launch_bounds__(256) void k_sm_mirror(double* __restrict__ P, doubl
     }
 }
 
-}  // namespace
-
-int pnmol_smooth_launch_build(hipStream_t st, int n, const double* P, const double* Ps, const double* m, const double* ms,
-                              const double* Kg, const SmoothConsts& c, int d, int dp, double* Gs, double* Pout, double* Psh,
-                              double* mh, double* dm) {
+// P^h, P- and P^h A^T into Pout / the sweep's tall matrix Gs, Ps^h into Psh, mh = m^h, dm = ms^h - A m^h
+int launch_build(hipStream_t st, int n, const double* P, const double* Ps, const double* m, const double* ms, const double* Kg,
+                 const SmoothConsts& c, int d, int dp, double* Gs, double* Pout, double* Psh, double* mh, double* dm) {
     const dim3 grid(dp / 32, dp / 8), blk(32, 8);
     switch (n) {
         case 2:
@@ -268,8 +268,9 @@ int pnmol_smooth_launch_build(hipStream_t st, int n, const double* P, const doub
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int pnmol_smooth_launch_finish(hipStream_t st, long Dp, const double* V, const double* T, const double* Psh, const double* mh,
-                               const double* dm, double* G, double* C, double* Pout, double* mout, double* var) {
+// from the sweep's V = P A^T L^-T and T = L^-T: G, C = G Ps^h, Pout = P^h - V V^T + C G^T (mirrored), var, mout = mh + G dm
+int launch_finish(hipStream_t st, long Dp, const double* V, const double* T, const double* Psh, const double* mh, const double* dm,
+                  double* G, double* C, double* Pout, double* mout, double* var) {
     const unsigned nt = (unsigned)((Dp + BM - 1) / BM);
     const dim3 grid(nt, nt);
     // G = V T^T  (T = L^-T upper triangular: column tile j0 needs k >= j0)
@@ -281,4 +282,113 @@ int pnmol_smooth_launch_finish(hipStream_t st, long Dp, const double* V, const d
     k_sm_mirror<<<dim3((unsigned)(Dp / 32), (unsigned)(Dp / 32)), dim3(32, 8), 0, st>>>(Pout, var, Dp);
     k_sm_mean<<<(unsigned)((Dp + 3) / 4), 256, 0, st>>>(G, mh, dm, mout, Dp);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// the tail of a smoother step: the sweep's info word, one stream synchronisation
+int smoother_step_wait(pnmol_filter* f, const pnmol_state* filt_k, double dt, pnmol_state* out) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    int inf = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&inf, f->sm_sweep.info, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    out->t = filt_k->t;
+    out->frame_dt = dt;
+    return sweep_info_result(ctx, inf, f->Dp, "pnmol_smoother_step", "predicted covariance not positive definite",
+                             "a dependency wait of the sweep timed out");
+}
+
+int smoother_step_impl(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt, pnmol_state* out,
+                       int keep_full, pnmol_bridge** bridge) {
+    if (bridge) *bridge = nullptr;
+    if (!f || !filt_k || !smooth_next || !out || out == filt_k || out == smooth_next || filt_k->f != f || smooth_next->f != f ||
+        out->f != f || !(dt > 0.0) || f->ds != f->d || f->p32) {
+        if (f) f->ctx->err = "pnmol_smoother_step: bad argument (null, aliasing, foreign state, dt <= 0, latent-force or fp32 filter)";
+        return -1;
+    }
+    pnmol_ctx* ctx = f->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = pnmol_smooth_ensure_ws(f);
+    if (rc != 0) return rc;
+    // everything in the Nordsieck frame of dt: ts / tsn move the two inputs there (as k_predict's IwpConsts.ts)
+    SmoothConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+    for (int a = 0; a < f->n; ++a) {
+        c.ts[a] = frame_ratio(f, a, filt_k->frame_dt, dt);
+        c.tsn[a] = frame_ratio(f, a, smooth_next->frame_dt, dt);
+    }
+    const long Dp = f->Dp;
+    const SweepWs& sw = f->sm_sweep;
+    double *mh = f->sm_vec, *dm = f->sm_vec + Dp;
+    rc = launch_build(st, f->n, filt_k->P, smooth_next->P, filt_k->mean, smooth_next->mean, f->Kg, c, f->d, f->dp, sw.G, out->P,
+                      f->sm_Psh, mh, dm);
+    if (rc != 0) {
+        ctx->err = "pnmol_smoother_step: kernel launch failed";
+        return rc;
+    }
+    if ((rc = sweep_ws_enqueue(f, sw, st, 0, "pnmol_smoother_step")) != 0) return rc;
+    const double* V = sw.F + Dp * Dp;
+    const double* T = sw.F + (2 * Dp + NB) * Dp;
+    rc = launch_finish(st, Dp, V, T, f->sm_Psh, mh, dm, f->sm_gain, f->sm_C, out->P, out->mean, out->var);
+    if (rc != 0) {
+        ctx->err = "pnmol_smoother_step: kernel launch failed";
+        return rc;
+    }
+    if (bridge) {
+        rc = pnmol_dense_make_bridge(f, filt_k, smooth_next, dt, out, c.tsn, keep_full, bridge);
+        if (rc != 0) return rc;
+    }
+    rc = smoother_step_wait(f, filt_k, dt, out);
+    if (rc != 0 && bridge && *bridge) {
+        pnmol_bridge_destroy(*bridge);
+        *bridge = nullptr;
+    }
+    return rc;
+}
+
+}  // namespace
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// The tall matrix of the backward step has the error model's layout with Dp columns: [P- (cb); P A^T (cb); zero block; I (cb)],
+// so the forward step's sweep launch factorises it as it is (strict pivots: P- >= Q1 (x) K is positive definite; the padded
+// points carry a unit pivot).  Allocated on first use, with G, C, Ps^h (Dp x Dp) and [m^h | dm] (2 Dp).
+void pnmol_smooth_free_ws(pnmol_filter* f) {
+    sweep_ws_free(&f->sm_sweep);
+    for (void* p : {(void*)f->sm_gain, (void*)f->sm_C, (void*)f->sm_Psh, (void*)f->sm_vec})
+        if (p) (void)hipFree(p);
+    f->sm_gain = f->sm_C = f->sm_Psh = f->sm_vec = nullptr;
+}
+
+int pnmol_smooth_ensure_ws(pnmol_filter* f) {
+    if (f->sm_sweep.G) return 0;
+    const long Dp = f->Dp;
+    const int cb = (int)(Dp / NB);
+    const size_t sq = (size_t)Dp * Dp;
+    hipError_t e = sweep_ws_alloc(&f->sm_sweep, f->ctx, 3 * cb + 1, cb);
+    if (e == hipSuccess) e = hipMalloc(&f->sm_gain, sizeof(double) * sq);
+    if (e == hipSuccess) e = hipMalloc(&f->sm_C, sizeof(double) * sq);
+    if (e == hipSuccess) e = hipMalloc(&f->sm_Psh, sizeof(double) * sq);
+    if (e == hipSuccess) e = hipMalloc(&f->sm_vec, sizeof(double) * 2 * (size_t)Dp);
+    if (e != hipSuccess) {
+        f->ctx->err = std::string("pnmol_smoother_step: workspace: ") + hipGetErrorString(e);
+        pnmol_smooth_free_ws(f);
+        return e == hipErrorOutOfMemory ? -4 : -2;
+    }
+    return 0;
+}
+
+int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                        pnmol_state* out) {
+    return smoother_step_impl(f, filt_k, smooth_next, dt, out, 0, nullptr);
+}
+
+int pnmol_smoother_step_bridge(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
+                               pnmol_state* out, int keep_full, pnmol_bridge** bridge) {
+    if (!bridge) {
+        if (f) f->ctx->err = "pnmol_smoother_step_bridge: bad argument (null bridge pointer)";
+        return -1;
+    }
+    return smoother_step_impl(f, filt_k, smooth_next, dt, out, keep_full, bridge);
 }

@@ -40,6 +40,8 @@ hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned f) { (void)f; *s = 
 hipError_t hipStreamDestroy(hipStream_t s) { free(s); return OK; }
 hipError_t hipStreamSynchronize(hipStream_t s) { (void)s; return OK; }
 hipError_t hipEventCreate(hipEvent_t* e) { *e = malloc(8); return OK; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned f) { (void)f; *e = malloc(8); return OK; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned f) { (void)s; (void)e; (void)f; return OK; }
 hipError_t hipEventDestroy(hipEvent_t e) { free(e); return OK; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { (void)e; (void)s; return OK; }
 hipError_t hipEventSynchronize(hipEvent_t e) { (void)e; return OK; }

@@ -1,4 +1,4 @@
-// Standalone timing of k_downdate<3> (N=512 sizes) for several chunk ranges.
+// Standalone timing of k_downdate<3> (N=512 sizes) for several chunk ranges.  Build: tools/README.md (as potrf_bench.hip).
 #include "../pnmol-experiments_amd/csrc/pnmol_hip.hip"
 #include <random>
 int main() {

@@ -1,6 +1,6 @@
 // Standalone timing harness for the 32x32 diagonal-block factorisations (not part of the product):
 // the two-wave column-at-a-time scheme (diag2w_from_lds) and the four-wave 4-column-blocked scheme (diag4_factor).
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude tools/potrf_bench.hip -o tools/potrf_bench
+// Build: tools/README.md (this file includes csrc/pnmol_hip.hip; the other csrc/*.hip go on the command line)
 #include "../pnmol-experiments_amd/csrc/pnmol_hip.hip"
 
 #include <random>
