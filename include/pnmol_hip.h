@@ -27,7 +27,8 @@
  *     2: `pnmol_sqrt_filter_create` refused `dtype = 1`, which now selects the fp32 QR of include/pnmol_sqrt.h).
  *     `pnmol_smoother_step` and the joint draws (`pnmol_samples_*`, `pnmol_sample_noise`) were added within version 3:
  *     backwards-compatible additions, nothing existing changed.  So was the dense output (`pnmol_state_predict*`,
- *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`).
+ *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`) and the measurement
+ *     update (`pnmol_state_observe`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -182,6 +183,29 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
  * filter; one stream synchronisation per call. */
 int pnmol_smoother_step(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_state* smooth_next, double dt,
                         pnmol_state* out);
+
+/* Measurement update: condition a state on sensor data -------------------------------------------------------------------------
+ * Model y = C E0 x + e, e ~ N(0, R_sqrtm R_sqrtm^T): q linear functionals of derivative 0 of the d_state state components (white-noise
+ * model: the solution u at the mesh points; latent-force model: [u; eps], so C has 2d columns).  No reference counterpart (the
+ * reference solves the PDE without data); the arithmetic is the covariance-form Kalman update of kalman.py:12-30 with the step's own
+ * Cholesky sweep.  With m, P of `in` and H = C E0:
+ *     S = H P H^T + R R^T = Ls Ls^T,   W = P H^T Ls^-T,   w = Ls^-1 (y - H m),   m_out = m + W w,   P_out = P - W W^T,
+ *     log_likelihood = log N(y; H m, S) = -1/2 (|w|^2 + 2 sum log Ls_ii + q log 2 pi),   mahalanobis = |w|^2,   logdet = log det S.
+ * `in` (any frame) is not modified; `out` (another state of the same filter) is an ordinary state at in's time in in's frame.
+ * C_q_ds (q, d_state) row-major; y_q (q); R_sqrtm_qq (q, q) lower triangular (the upper part is ignored) or NULL: noise-free.
+ * The covariances are the uncalibrated ones the states carry (sigma^2 = 1): R is weighed against that prior.
+ * fp64 filters, white-noise and latent-force.  -1: null or aliased pointers, a state of another filter, q < 1, q > d_state, an fp32
+ * filter.  -3: S not positive definite, e.g. duplicate rows of C without noise (res->info and `pnmol_last_error` name the pivot; `out`
+ * is undefined then).  -4: out of memory.  Workspace (~2 (Dp + q) q doubles per distinct round_up(q, 32)) is allocated on first use and
+ * kept by the filter; one stream synchronisation per call. */
+typedef struct pnmol_observe_out {
+    double log_likelihood;
+    double mahalanobis;
+    double logdet;
+    int info; /* -1 ok, else index of the first non-positive pivot of S */
+} pnmol_observe_out;
+int pnmol_state_observe(pnmol_filter* f, const pnmol_state* in, int q, const double* C_q_ds, const double* y_q,
+                        const double* R_sqrtm_qq, pnmol_state* out, pnmol_observe_out* res);
 
 /* Dense output: the posterior BETWEEN grid times ------------------------------------------------------------------------------
  * Between two grid times there is no measurement, so given the states at the two ends of a step the state at t inside it follows

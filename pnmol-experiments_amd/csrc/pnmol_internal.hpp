@@ -71,6 +71,15 @@ int sweep_ws_enqueue(pnmol_filter* f, const SweepWs& w, hipStream_t st, int leni
 int sweep_info_result(pnmol_ctx* ctx, int inf, long limit, const char* who, const char* what,
                       const char* wait = "a dependency wait timed out");
 
+// Workspace of a measurement update with qp padded columns (pnmol_state_observe, pnmol_observe.hip): the sweep of the tall matrix
+// [S; B; v^T] and one device block [H (qp x dp) | R (qp x qp) | y (qp) | the call's scalars (4)] with the host image of its inputs
+struct ObserveWs {
+    int qp = 0;
+    SweepWs sweep;
+    double* dev = nullptr;
+    std::vector<double> host;
+};
+
 struct pnmol_filter {
     pnmol_ctx* ctx = nullptr;
     int d = 0, n = 0, nu = 0, nB = 0, m = 0, dp = 0, mp = 0, CB = 0, RBS = 0, RBW = 0, RT = 0, ellw = 0;
@@ -159,6 +168,8 @@ struct pnmol_filter {
     void* dn_scratch = nullptr;
     size_t dn_cap = 0;
     struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
+    // Measurement updates (pnmol_state_observe): one workspace per padded column count, allocated on first use
+    std::vector<ObserveWs*> ob_ws;
 };
 
 struct pnmol_state {
@@ -231,6 +242,7 @@ inline void small_cholesky(int n, const double* A, double* L, bool semidefinite 
 void pnmol_smooth_free_ws(pnmol_filter* f);
 void pnmol_sample_free_ws(pnmol_filter* f);
 void pnmol_dense_free_ws(pnmol_filter* f);
+void pnmol_observe_free_ws(pnmol_filter* f);
 // pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
 

@@ -29,6 +29,17 @@ class StepOut(ctypes.Structure):
     ]
 
 
+class ObserveOut(ctypes.Structure):
+    """`pnmol_observe_out`: log N(y; H m, S), |Ls^-1 (y - H m)|^2, log det S, info (-1 ok, else the failing pivot)."""
+
+    _fields_ = [
+        ("log_likelihood", ctypes.c_double),
+        ("mahalanobis", ctypes.c_double),
+        ("logdet", ctypes.c_double),
+        ("info", ctypes.c_int),
+    ]
+
+
 class FilterDesc(ctypes.Structure):
     _fields_ = [
         ("d", ctypes.c_int),
@@ -76,6 +87,8 @@ SYMBOLS = {
     "pnmol_filter_step": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp, ctypes.POINTER(StepOut), _c_double_p]),
     "pnmol_smoother_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "pnmol_state_predict": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp]),
+    "pnmol_state_observe": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _vp,
+                                           ctypes.POINTER(ObserveOut)]),
     "pnmol_state_predict_marginals": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p]),
     "pnmol_smoother_step_bridge": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
     "pnmol_bridge_destroy": (ctypes.c_int, [_vp]),
@@ -395,6 +408,21 @@ class Filter:
         t = ctypes.c_double(0.0)
         self.lib.pnmol_state_get_time(out.handle, ctypes.byref(t))
         return out, Bridge(self, h, (t.value, float(dt), bridge == "full"))
+
+    def observe(self, state, C, y, R_sqrtm=None):
+        """Condition `state` on y = C E0 x + e, e ~ N(0, R_sqrtm R_sqrtm^T) (`pnmol_state_observe`): (new State at the same
+        time and in the same frame, ObserveOut).  C (q, d_state), y (q,), R_sqrtm (q, q) lower triangular or None (noise-free)."""
+        C = _f64(C)
+        if C.ndim != 2 or C.shape[1] != self.ds or not 1 <= C.shape[0] <= self.ds:
+            raise ValueError(f"C must be (q, {self.ds}) with 1 <= q <= {self.ds}, got {C.shape}")
+        q = C.shape[0]
+        y = _f64(y, (q,))
+        R = None if R_sqrtm is None else _f64(R_sqrtm, (q, q))
+        out, res = State(self), ObserveOut()
+        rc = self.lib.pnmol_state_observe(self.handle, state.handle, q, _dp(C), _dp(y), None if R is None else _dp(R),
+                                          out.handle, ctypes.byref(res))
+        self.ctx.check(rc, "pnmol_state_observe")
+        return out, res
 
     def predict(self, state, dt):
         """The prior alone carried over dt > 0 from `state` (`pnmol_state_predict`): a new State at state.t + dt."""

@@ -164,12 +164,37 @@ class PDEFilter(ABC):
         cov_sqrtm_new = state.y.cov_sqrtm * np.sqrt(np.mean(np.array(d2)))
         return state._replace(y=state.y._replace(cov_sqrtm=cov_sqrtm_new)), info
 
-    def solution_generator(self, pde, /, *, stop_at=None, progressbar=False):
-        """Generate solver steps, starting with the initial state (pdefilter.py:118-165)."""
+    def _check_observations_supported(self):
+        raise TypeError(f"{type(self).__name__} does not take observations")
+
+    def _observe(self, state, observation):
+        raise NotImplementedError
+
+    def solution_generator(self, pde, /, *, stop_at=None, progressbar=False, observations=None):
+        """Generate solver steps, starting with the initial state (pdefilter.py:118-165).
+
+        observations (beyond the reference): a sequence of `pnmol.data.Observation`, sorted by t.  The accepted step that lands
+        on an observation's time (`pnmol.data.times_agree`) is followed by the measurement update on the device, and the updated
+        state is what is yielded; an observation at pde.t0 updates the initial state.  `Constant` steps: every observation time
+        must be a grid time (ValueError otherwise, before any device work); `Adaptive`: the times are merged into `stop_at`.
+        `info` then carries `data_log_likelihood` (the sum) and `data_log_likelihoods` (one entry per observation): log p(y_k |
+        y_1..k-1, PDE) under the uncalibrated (sigma^2 = 1) prior, against which the observation noise is weighed."""
+        pending = None
+        if observations is not None:
+            from . import data
+
+            self._check_observations_supported()
+            pending = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
+            if not isinstance(self.steprule, step.Constant):
+                stops = data.merged_stops(stop_at, pending, pde.t0)
+                stop_at = stops if stops else None
         time_stopper = _TimeStopper(stop_at) if stop_at is not None else None
         state = self.initialize(pde)
         info = dict(num_f_evaluations=0, num_df_evaluations=0, num_df_diagonal_evaluations=0, num_steps=0,
                     num_attempted_steps=0)
+        if pending is not None:
+            info["data_log_likelihood"], info["data_log_likelihoods"] = 0.0, []
+            state = self._apply_due_observations(state, pending, info, self.steprule.first_dt(pde))
         yield state, info
         dt = self.steprule.first_dt(pde)
         pbar = None
@@ -185,15 +210,31 @@ class PDEFilter(ABC):
                 pbar.set_description(f"t={state.t:.4f}, dt={dt:.2E}")
             if time_stopper is not None:
                 dt = time_stopper.adjust_dt_to_time_stops(state.t, dt)
+            t_before = state.t
             state, dt, step_info = self.perform_full_step(state, dt, pde)
             info["num_steps"] += 1
             for key in ("num_f_evaluations", "num_df_evaluations", "num_df_diagonal_evaluations",
                         "num_attempted_steps"):
                 info[key] += step_info[key]
+            if pending:
+                state = self._apply_due_observations(state, pending, info, state.t - t_before)
             yield state, info
         if pbar is not None:
             pbar.update()
             pbar.close()
+
+    def _apply_due_observations(self, state, pending, info, dt):
+        """Condition `state` on the head of `pending` if its time is state.t (dt: the step just taken); a time the loop has
+        stepped over is an error (it cannot happen with the checks of `pnmol.data.prepare` and the merged stops)."""
+        from . import data
+
+        if pending and data.times_agree(pending[0].t, state.t, dt):
+            state, log_likelihood = self._observe(state, pending.pop(0))
+            info["data_log_likelihoods"].append(log_likelihood)
+            info["data_log_likelihood"] += log_likelihood
+        if pending and pending[0].t < state.t:
+            raise RuntimeError(f"the step to t={state.t} passed the observation at t={pending[0].t}")
+        return state
 
     def perform_full_step(self, state, initial_dt, pde):
         """One accepted step incl. the accept/reject loop of the step rule (pdefilter.py:177-227)."""

@@ -263,6 +263,28 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             y=rv.DeviceMultivariateNormal(m_new, dev_out), diffusion_squared_local=info.diffusion_squared_local)
         return new_state, dict(num_f_evaluations=1, num_df_evaluations=1)
 
+    # ------------------------------------------------------------------ sensor data
+    def _check_observations_supported(self):
+        from . import sqrtform
+
+        if isinstance(self, sqrtform._SqrtFormMixin) or self.dtype != "f64":
+            raise TypeError(f"observations are supported by the fp64 covariance-form solvers of pnmol.white and pnmol.latent; "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+
+    def _observe(self, state, observation):
+        """`state` conditioned on `observation` (`pnmol_state_observe`): (new state at the same time,
+        log-likelihood of the data).  The observation reads derivative 0 of the solution components; the eps half of a
+        latent-force state gets zero columns.  `diffusion_squared_local` keeps its meaning (PDE residuals only)."""
+        flt = self._device_filter
+        dev_in = self._device_state_of(state, self._device_pde)
+        C = observation.C
+        if C.shape[1] != flt.ds:
+            C = np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
+        dev_out, res = flt.observe(dev_in, C, observation.y, observation.R_sqrtm)
+        m_new = dev_out.mean()
+        ref = None if state.reference_state is None else np.abs(m_new[0][:observation.C.shape[1]])
+        return state._replace(y=rv.DeviceMultivariateNormal(m_new, dev_out), reference_state=ref), res.log_likelihood
+
     def solve_marginals(self, pde, *, num_steps=None):
         """Constant-step solve that keeps everything on the device: returns
         (t (T+1,), means (T+1,d), stds (T+1,d), diffusion_squared_local (T,), final PDEFilterState).
