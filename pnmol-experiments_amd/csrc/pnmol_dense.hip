@@ -6,13 +6,14 @@
 //     x_t | x_l, x_r ~ N((Bm (x) I) x_l + (Bp (x) I) x_r, Qb (x) K)
 //     Ps_t = Bm Pl Bm^T + Bm C Bp^T + (Bm C Bp^T)^T + Bp Pr Bp^T + Qb (x) K,     C = Cov(x_l, x_r | data)
 // block by block over pairs of mesh points: no factorisation, no product longer than n.  Everything here is element-wise in the
-// mesh points and memory-bound; no MFMA.  Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp,
-// row-major, zero padding (dp is a multiple of 32).
+// mesh points and memory-bound; no MFMA (of pnmol_tile.hpp this file uses predict_block alone, in k_dn_predict).  Layouts are
+// the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp, row-major, zero padding (dp is a multiple of 32).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_tile.hpp"
 
 namespace {
 
@@ -106,37 +107,26 @@ __global__ __launch_bounds__(256) void k_dn_eval(const double* __restrict__ blk,
     }
 }
 
-// the predict half of the smoother's block transform: Pout = A1 (ts ts^T o P) A1^T + Q1 K, block by block
+// the predict half of the smoother's block transform (predict_block of pnmol_tile.hpp): Pout = A1 (ts ts^T o P) A1^T + Q1 K,
+// block by block
 template <int N>
 __global__ __launch_bounds__(256) void k_dn_predict(const double* __restrict__ P, const double* __restrict__ Kg, SmoothConsts c,
                                                     int dp, double* __restrict__ Pout, double* __restrict__ var) {
     const int k = blockIdx.x * 32 + threadIdx.x;
     const int j = blockIdx.y * 8 + threadIdx.y;
     const long Dp = (long)N * dp;
-    double X[N][N], XA[N][N];
+    double X[N][N], XA[N][N], Pm[N][N];
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
         for (int b = 0; b < N; ++b) X[a][b] = c.ts[a] * c.ts[b] * P[((long)a * dp + j) * Dp + (long)b * dp + k];
-    const double kjk = Kg[(long)j * dp + k];
+    predict_block<N>(X, c.A1, c.Q1, Kg[(long)j * dp + k], XA, Pm);
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
         for (int b = 0; b < N; ++b) {
-            double s = 0.0;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += X[a][e] * c.A1[b * SM_MAXN + e];
-            XA[a][b] = s;
-        }
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-            double s = c.Q1[a * SM_MAXN + b] * kjk;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += c.A1[a * SM_MAXN + e] * XA[e][b];
-            Pout[((long)a * dp + j) * Dp + (long)b * dp + k] = s;
-            if (a == b && j == k) var[(long)a * dp + j] = s;
+            Pout[((long)a * dp + j) * Dp + (long)b * dp + k] = Pm[a][b];
+            if (a == b && j == k) var[(long)a * dp + j] = Pm[a][b];
         }
 }
 

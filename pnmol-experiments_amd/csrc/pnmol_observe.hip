@@ -6,115 +6,21 @@
 //     [S; B; v^T]  --sweep-->  [Ls; W = B Ls^-T; w^T = v^T Ls^-T]          (the forward step's own Cholesky launch, strict pivots)
 //     m_out = m + W w,   P_out = P - W W^T,   log p(y) = -1/2 (|w|^2 + 2 sum log Ls_ii + q log 2 pi)
 // Columns are padded to qp (a multiple of 32, at least 64: the smallest tall shape the sweep runs elsewhere); the padded pivots
-// carry a unit diagonal, the padded rows of H are zero.  Every product runs on one LDS-staged fp64 MFMA tile routine (the
-// pattern of pnmol_smooth.hip's gemm_pass): the thin product B (k_ob_thin), S and the v^T row block (k_ob_build), and the
-// down-date P - W W^T on lower 64 x 64 tiles, mirrored through LDS, with the marginal variances (k_ob_syrk).
+// carry a unit diagonal, the padded rows of H are zero.  Every product runs on one LDS-staged fp64 MFMA tile routine
+// (tile_product of pnmol_tile.hpp, which the smoother's GEMM uses too): the thin product B (k_ob_thin), S and the v^T row
+// block (k_ob_build), and the down-date P - W W^T on lower 64 x 64 tiles, mirrored through LDS, with the marginal variances
+// (k_ob_syrk).
 // Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp, row-major, zero padding.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_tile.hpp"
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 64;       // output tile (rows = cols)
-constexpr int BK = 16;       // K step staged in LDS
-constexpr int LDT = BM + 2;  // LDS row pitch of a k-major operand tile (doubles)
 constexpr int LDO = BM + 1;  // LDS row pitch of an output tile image
-
-// a 64 x 16 block of X (rows r0.., cols k0.., row pitch ld; rows >= nrows read as zero): thread -> row tid / 4, four consecutive k
-__device__ __forceinline__ void stage_rows(const double* __restrict__ X, long ld, long nrows, long r0, long k0, double (&v)[4],
-                                           int tid) {
-    const long r = r0 + (tid >> 2);
-    const long k = k0 + 4 * (tid & 3);
-    if (r < nrows) {
-        const double2* p = reinterpret_cast<const double2*>(X + r * ld + k);
-        const double2 a = p[0], b = p[1];
-        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-    } else {
-        v[0] = v[1] = v[2] = v[3] = 0.0;
-    }
-}
-// a 16 x 64 block of X (rows k0.., cols c0..; cols >= ncols read as zero): thread -> row tid / 16, four consecutive columns
-__device__ __forceinline__ void stage_cols(const double* __restrict__ X, long ld, long ncols, long c0, long k0, double (&v)[4],
-                                           int tid) {
-    const long k = k0 + (tid >> 4);
-    const long c = c0 + 4 * (tid & 15);
-    if (c < ncols) {
-        const double2* p = reinterpret_cast<const double2*>(X + k * ld + c);
-        const double2 a = p[0], b = p[1];
-        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-    } else {
-        v[0] = v[1] = v[2] = v[3] = 0.0;
-    }
-}
-__device__ __forceinline__ void put_rows(double* s, const double (&v)[4], int tid) {  // s[k][row]
-    const int r = tid >> 2, k = 4 * (tid & 3);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[(k + e) * LDT + r] = v[e];
-}
-__device__ __forceinline__ void put_cols(double* s, const double (&v)[4], int tid) {  // s[k][col]
-    const int k = tid >> 4, c = 4 * (tid & 15);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[k * LDT + c + e] = v[e];
-}
-
-// acc += the 64 x 64 tile (r0, c0) of A op(B) over K (a multiple of BK).  A: rows x K, row pitch lda, rows >= arows zero.
-// NT: op(B) = B^T, B: cols x K like A (rows >= bext zero).  !NT: B: K x cols, row pitch ldb, columns >= bext zero (a multiple
-// of 4).  Four waves, 2 x 2, each 32 x 32 = 2 x 2 blocks of v_mfma_f64_16x16x4_f64; the next K block is in flight while this
-// one is multiplied.
-template <bool NT>
-__device__ __forceinline__ void tile_product(const double* __restrict__ A, long lda, long arows, const double* __restrict__ B,
-                                             long ldb, long bext, long K, long r0, long c0, d4 (&acc)[2][2], double* sA,
-                                             double* sB, int tid) {
-    const int l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
-    double va[4], vb[4];
-    stage_rows(A, lda, arows, r0, 0, va, tid);
-    if (NT) stage_rows(B, ldb, bext, c0, 0, vb, tid);
-    else stage_cols(B, ldb, bext, c0, 0, vb, tid);
-    d4 part[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) part[i][j] = d4{0, 0, 0, 0};
-    for (long k0 = 0; k0 < K; k0 += BK) {
-        __syncthreads();
-        put_rows(sA, va, tid);
-        if (NT) put_rows(sB, vb, tid);
-        else put_cols(sB, vb, tid);
-        __syncthreads();
-        if (k0 + BK < K) {
-            stage_rows(A, lda, arows, r0, k0 + BK, va, tid);
-            if (NT) stage_rows(B, ldb, bext, c0, k0 + BK, vb, tid);
-            else stage_cols(B, ldb, bext, c0, k0 + BK, vb, tid);
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 4) {
-            const int kr = kk + (l >> 4);
-            double a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = sA[kr * LDT + wr * 32 + i * 16 + (l & 15)];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = sB[kr * LDT + wc * 32 + j * 16 + (l & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) part[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], part[i][j], 0, 0, 0);
-        }
-    }
-    // the accumulators are read behind the loop's exit branch: wait states by hand (as in pnmol_smooth.hip's gemm_pass;
-    // tests/test_observe_isa_hazards.py scans this file)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] += part[i][j];
-}
 
 // B = P[:, block 0] H^T into the rows [qp, qp + Dp) of the sweep's tall matrix (Gb: row pitch qp).  Hp: qp x dp, the rows of
 // H = sc[0] C padded with zeros, so the contraction runs over the dp columns of derivative block 0.
@@ -122,25 +28,14 @@ __global__ __launch_bounds__(256) void k_ob_thin(const double* __restrict__ P, l
                                                  int qp, double* __restrict__ Gb) {
     __shared__ __attribute__((aligned(16))) double sA[BK * LDT];
     __shared__ __attribute__((aligned(16))) double sB[BK * LDT];
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int tid = threadIdx.x;
     const long r0 = (long)blockIdx.y * BM, c0 = (long)blockIdx.x * BM;
     d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0, 0, 0, 0};
-    tile_product<true>(P, Dp, Dp, Hp, dp, qp, dp, r0, c0, acc, sA, sB, tid);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const long col = c0 + wc * 32 + j * 16 + (l & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long row = r0 + wr * 32 + i * 16 + (l >> 4) + 4 * r;
-                if (row < Dp && col < qp) Gb[row * qp + col] = acc[i][j][r];
-            }
-        }
+    tile_zero(acc);
+    tile_product<true>(P, Dp, Dp, Hp, dp, qp, dp, 0, 1.0, r0, c0, acc, sA, sB, tid);
+    tile_each(acc, r0, c0, tid, [&](long row, long col, double v) {
+        if (row < Dp && col < qp) Gb[row * qp + col] = v;
+    });
 }
 
 // The rest of the tall matrix.  Blocks [0, nS^2): a 64 x 64 tile of S = Hp B[block 0] + Rp Rp^T (rows [0, qp) of G; Rp = R
@@ -152,7 +47,7 @@ __global__ __launch_bounds__(256) void k_ob_build(const double* __restrict__ Hp,
                                                   double* __restrict__ Gv) {
     __shared__ __attribute__((aligned(16))) double sA[BK * LDT];
     __shared__ __attribute__((aligned(16))) double sB[BK * LDT];
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
     if ((int)blockIdx.x >= nS * nS) {
         const int r = ((int)blockIdx.x - nS * nS) * 4 + w;
         if (r >= qp) return;
@@ -165,23 +60,12 @@ __global__ __launch_bounds__(256) void k_ob_build(const double* __restrict__ Hp,
     }
     const long r0 = (long)(blockIdx.x / nS) * BM, c0 = (long)(blockIdx.x % nS) * BM;
     d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0, 0, 0, 0};
-    tile_product<false>(Hp, dp, qp, Gb, qp, qp, dp, r0, c0, acc, sA, sB, tid);
-    if (Rp) tile_product<true>(Rp, qp, qp, Rp, qp, qp, qp, r0, c0, acc, sA, sB, tid);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const long col = c0 + wc * 32 + j * 16 + (l & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long row = r0 + wr * 32 + i * 16 + (l >> 4) + 4 * r;
-                if (row < qp && col < qp) G[row * qp + col] = (row == col && row >= q) ? 1.0 : acc[i][j][r];
-            }
-        }
+    tile_zero(acc);
+    tile_product<false>(Hp, dp, qp, Gb, qp, qp, dp, 0, 1.0, r0, c0, acc, sA, sB, tid);
+    if (Rp) tile_product<true>(Rp, qp, qp, Rp, qp, qp, qp, 0, 1.0, r0, c0, acc, sA, sB, tid);
+    tile_each(acc, r0, c0, tid, [&](long row, long col, double v) {
+        if (row < qp && col < qp) G[row * qp + col] = (row == col && row >= q) ? 1.0 : v;
+    });
 }
 
 // Pout = Pin - W W^T (W: Dp x qp) and var = diag(Pout).  One workgroup per lower 64 x 64 tile (Dp is a multiple of 32, not
@@ -194,22 +78,13 @@ __global__ __launch_bounds__(256) void k_ob_syrk(const double* __restrict__ W, i
     __shared__ double sT[BM * LDO];
     const int bi = blockIdx.y, bj = blockIdx.x;
     if (bj > bi) return;
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int tid = threadIdx.x;
     const long r0 = (long)bi * BM, c0 = (long)bj * BM;
     const bool diag = bi == bj;
     d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0, 0, 0, 0};
-    tile_product<true>(W, qp, Dp, W, qp, Dp, qp, r0, c0, acc, sA, sB, tid);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sT[(wr * 32 + i * 16 + (l >> 4) + 4 * r) * LDO + wc * 32 + j * 16 + (l & 15)] = acc[i][j][r];
+    tile_zero(acc);
+    tile_product<true>(W, qp, Dp, W, qp, Dp, qp, 0, 1.0, r0, c0, acc, sA, sB, tid);
+    tile_each(acc, 0, 0, tid, [&](long r, long c, double v) { sT[r * LDO + c] = v; });  // (tile-local)
     __syncthreads();
     // the tile itself (a diagonal tile: its lower half), rows of 64 consecutive doubles
     for (int e = tid; e < BM * BM; e += 256) {

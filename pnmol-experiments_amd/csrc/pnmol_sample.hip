@@ -5,8 +5,8 @@
 //     xt = m + s C xi_1,    r = x_{k+1} - A xt - s Gamma_Q xi_2,    x_k = xt + G r,    G = P A^T (P-)^-1
 // The gain is never formed: the smoother's sweep [P-; P A^T; 0; I] -> [L; V; 0; T] (T = L^-T) gives G r = V (T^T r), two
 // thin products.  This file holds what surrounds the two sweeps (pnmol_hip.hip): the block transform with the frame change
-// (k_sp_build), the counter-based generator (k_sp_noise), the thin product on the fp64 MFMA (k_sp_thin), the n x n mixes
-// (k_sp_resid) and the read-out (k_sp_get).
+// (k_sp_build; its predict is predict_block of pnmol_tile.hpp, shared with the smoother), the counter-based generator
+// (k_sp_noise), the thin product on the fp64 MFMA (k_sp_thin), the n x n mixes (k_sp_resid) and the read-out (k_sp_get).
 // Layouts: a sample block is Dp x Sp row-major, row = state component (derivative-major (a, j) -> a*dp + j like a mean),
 // column = draw; Sp is a multiple of 64; padding rows and columns are zero.
 #include <hip/hip_runtime.h>
@@ -14,10 +14,9 @@
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_tile.hpp"
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // ---- build ----------------------------------------------------------------------------------------------------------------
 // P (frame of the filtered state) -> frame of h:
@@ -25,7 +24,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 //                        sweep drops what is not positive)
 //   Gs rows [0, Dp):     P- = A1 P^h A1^T + Q1 K   (+1 on the diagonal of the padded points)
 //   Gs rows [Dp, 2Dp):   P^h A1^T
-// (k_sm_build of pnmol_smooth.hip without the smoothed successor)
+// (k_sm_build of pnmol_smooth.hip without the smoothed successor; the predict is predict_block of pnmol_tile.hpp)
 template <int N>
 __global__ __launch_bounds__(256) void k_sp_build(const double* __restrict__ P, const double* __restrict__ Kg, SampleConsts c,
                                                   int d, int dp, double* __restrict__ Gc, double* __restrict__ Gs) {
@@ -56,27 +55,14 @@ __global__ __launch_bounds__(256) void k_sp_build(const double* __restrict__ P, 
             Gc[((long)j * N + a) * Dp + (long)k * N + b] = (pad && a == b) ? 1.0 : X[a][b];
         }
     if (!Gs) return;
-    const double kjk = Kg[(long)j * dp + k];
-    double XA[N][N];
+    double XA[N][N], Pm[N][N];
+    predict_block<N>(X, c.A1, c.Q1, Kg[(long)j * dp + k], XA, Pm);
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
         for (int b = 0; b < N; ++b) {
-            double s = 0.0;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += X[a][e] * c.A1[b * SM_MAXN + e];
-            XA[a][b] = s;
-            Gs[(Dp + (long)a * dp + j) * Dp + (long)b * dp + k] = s;
-        }
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-            double s = c.Q1[a * SM_MAXN + b] * kjk;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += c.A1[a * SM_MAXN + e] * XA[e][b];
-            if (a == b && pad) s = 1.0;
-            Gs[((long)a * dp + j) * Dp + (long)b * dp + k] = s;
+            Gs[(Dp + (long)a * dp + j) * Dp + (long)b * dp + k] = XA[a][b];
+            Gs[((long)a * dp + j) * Dp + (long)b * dp + k] = (a == b && pad) ? 1.0 : Pm[a][b];
         }
 }
 
@@ -248,8 +234,8 @@ __global__ __launch_bounds__(256) void k_sp_thin(ThinArgs g) {
             }
         }
     }
-    // the accumulators are read behind the loop's exit branch: wait states by hand (as in pnmol_smooth.hip's gemm_pass;
-    // tests/test_sample_isa_hazards.py scans this file)
+    // the accumulators are read behind the loop's exit branch: wait states by hand (as in tile_product of pnmol_tile.hpp;
+    // tests/test_isa_hazards.py scans this file)
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);

@@ -5,22 +5,18 @@
 //     P- = A P A^T + Q,   [P-; P A^T; 0; I]  --sweep-->  [L; V; 0; T]    (L L^T = P-,  V = P A^T L^-T,  T = L^-T)
 //     G  = V T^T  (= P A^T P-^-1),   C = G Ps,   Ps_k = P - V V^T + C G^T,   ms_k = m + G (ms - A m)
 // The sweep is the forward step's own Cholesky launch (pnmol_hip.hip); this file holds what surrounds it: the n x n block
-// transform with the frame change (k_sm_build), the vector part (k_sm_vec, k_sm_mean), one LDS-staged fp64 MFMA GEMM for
-// every product (k_sm_gemm) and the mirror of the lower-half results with the marginal variances (k_sm_mirror).
+// transform with the frame change (k_sm_build; its predict is predict_block of pnmol_tile.hpp), the vector part (k_sm_vec,
+// k_sm_mean), one LDS-staged fp64 MFMA GEMM for every product (k_sm_gemm, on tile_product of pnmol_tile.hpp) and the mirror of
+// the lower-half results with the marginal variances (k_sm_mirror).
 // Layouts are the forward step's: derivative-major (a, j) -> a*dp + j, Dp = n*dp, row-major, zero padding.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_tile.hpp"
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 64;    // output tile (rows = cols)
-constexpr int BK = 16;    // K step staged in LDS
-constexpr int LDT = BM + 2;  // LDS row pitch of a k-major tile (doubles)
 
 // P (frame of the filtered state) and Ps (frame of the smoothed successor) -> frame of h:
 //   Gs rows [0, Dp):     P- = A1 P^h A1^T + Q1 K   (+1 on the diagonal of the padded points: the sweep needs a pivot)
@@ -44,28 +40,14 @@ __global__ __launch_bounds__(256) void k_sm_build(const double* __restrict__ P, 
             Pout[idx] = X[a][b];
             Psh[idx] = c.tsn[a] * c.tsn[b] * Ps[idx];
         }
-    const double kjk = Kg[(long)j * dp + k];
-    // XA = X A1^T  (rows of P A^T),  Pm = A1 XA + Q1 K
-    double XA[N][N];
+    double XA[N][N], Pm[N][N];
+    predict_block<N>(X, c.A1, c.Q1, Kg[(long)j * dp + k], XA, Pm);
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
         for (int b = 0; b < N; ++b) {
-            double s = 0.0;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += X[a][e] * c.A1[b * SM_MAXN + e];
-            XA[a][b] = s;
-            Gs[(Dp + (long)a * dp + j) * Dp + (long)b * dp + k] = s;
-        }
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-            double s = c.Q1[a * SM_MAXN + b] * kjk;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += c.A1[a * SM_MAXN + e] * XA[e][b];
-            if (a == b && j == k && j >= d) s = 1.0;
-            Gs[((long)a * dp + j) * Dp + (long)b * dp + k] = s;
+            Gs[(Dp + (long)a * dp + j) * Dp + (long)b * dp + k] = XA[a][b];
+            Gs[((long)a * dp + j) * Dp + (long)b * dp + k] = (a == b && j == k && j >= d) ? 1.0 : Pm[a][b];
         }
 }
 
@@ -106,7 +88,7 @@ __global__ __launch_bounds__(256) void k_sm_mean(const double* __restrict__ G, c
 // C (+)= alpha1 op(A1) op(B1) [+ alpha2 A2 B2^T] on 64 x 64 tiles, M = N = K = Dp (a multiple of 32, not always of 64:
 // the edge tiles load zeros and store nothing outside).  op(B) = B^T (nt) or B.  lower: tiles above the diagonal are
 // skipped (symmetric results; k_sm_mirror fills them).  b_upper_nt: B is upper triangular and op(B) = B^T, so column
-// tile j0 only needs k >= j0.  Four waves, 2 x 2, each 32 x 32 = 2 x 2 blocks of v_mfma_f64_16x16x4_f64.
+// tile j0 only needs k >= j0.  The tile routine is tile_product of pnmol_tile.hpp.
 struct GemmArgs {
     const double* A1;
     const double* B1;
@@ -118,117 +100,25 @@ struct GemmArgs {
     int nt1, lower, accumulate, b_upper_nt;
 };
 
-__device__ __forceinline__ void stage_rows(const double* __restrict__ X, long n, long r0, long k0, double (&v)[4], int tid) {
-    // a 64 x 16 block of X (rows r0.., cols k0..): thread -> row tid / 4, four consecutive k
-    const long r = r0 + (tid >> 2);
-    const long k = k0 + 4 * (tid & 3);
-    if (r < n) {
-        const double2* p = reinterpret_cast<const double2*>(X + r * n + k);
-        const double2 a = p[0], b = p[1];
-        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-    } else {
-        v[0] = v[1] = v[2] = v[3] = 0.0;
-    }
-}
-__device__ __forceinline__ void stage_cols(const double* __restrict__ X, long n, long c0, long k0, double (&v)[4], int tid) {
-    // a 16 x 64 block of X (rows k0.., cols c0..): thread -> row tid / 16, four consecutive columns
-    const long k = k0 + (tid >> 4);
-    const long c = c0 + 4 * (tid & 15);
-    if (c < n) {
-        const double2* p = reinterpret_cast<const double2*>(X + k * n + c);
-        const double2 a = p[0], b = p[1];
-        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-    } else {
-        v[0] = v[1] = v[2] = v[3] = 0.0;
-    }
-}
-__device__ __forceinline__ void put_rows(double* s, const double (&v)[4], int tid) {  // s[k][row]
-    const int r = tid >> 2, k = 4 * (tid & 3);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[(k + e) * LDT + r] = v[e];
-}
-__device__ __forceinline__ void put_cols(double* s, const double (&v)[4], int tid) {  // s[k][col]
-    const int k = tid >> 4, c = 4 * (tid & 15);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[k * LDT + c + e] = v[e];
-}
-
-__device__ __forceinline__ void gemm_pass(const double* __restrict__ A, const double* __restrict__ B, bool nt, long n, long r0,
-                                          long c0, long kbeg, double alpha, d4 (&acc)[2][2], double* sA, double* sB, int tid) {
-    const int l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
-    double va[4], vb[4];
-    stage_rows(A, n, r0, kbeg, va, tid);
-    if (nt) stage_rows(B, n, c0, kbeg, vb, tid);
-    else stage_cols(B, n, c0, kbeg, vb, tid);
-    d4 part[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) part[i][j] = d4{0, 0, 0, 0};
-    for (long k0 = kbeg; k0 < n; k0 += BK) {
-        __syncthreads();
-        put_rows(sA, va, tid);
-        if (nt) put_rows(sB, vb, tid);
-        else put_cols(sB, vb, tid);
-        __syncthreads();
-        if (k0 + BK < n) {  // next block in flight while this one is multiplied
-            stage_rows(A, n, r0, k0 + BK, va, tid);
-            if (nt) stage_rows(B, n, c0, k0 + BK, vb, tid);
-            else stage_cols(B, n, c0, k0 + BK, vb, tid);
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 4) {
-            const int kr = kk + (l >> 4);
-            double a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = sA[kr * LDT + wr * 32 + i * 16 + (l & 15)];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = sB[kr * LDT + wc * 32 + j * 16 + (l & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) part[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], part[i][j], 0, 0, 0);
-        }
-    }
-    // the accumulators are read behind the loop's exit branch: wait states by hand (mfma_result_guard in pnmol_hip.hip;
-    // tests/test_smooth_isa_hazards.py scans this file)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] += alpha * part[i][j];
-}
-
 __global__ __launch_bounds__(256) void k_sm_gemm(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) double sA[BK * LDT];
     __shared__ __attribute__((aligned(16))) double sB[BK * LDT];
     const int bi = blockIdx.y, bj = blockIdx.x;
     if (g.lower && bj > bi) return;
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int tid = threadIdx.x;
     const long r0 = (long)bi * BM, c0 = (long)bj * BM, n = g.n;
     d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0, 0, 0, 0};
-    gemm_pass(g.A1, g.B1, g.nt1 != 0, n, r0, c0, g.b_upper_nt ? c0 : 0, g.alpha1, acc, sA, sB, tid);
-    if (g.A2) gemm_pass(g.A2, g.B2, true, n, r0, c0, 0, g.alpha2, acc, sA, sB, tid);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const long col = c0 + wc * 32 + j * 16 + (l & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long row = r0 + wr * 32 + i * 16 + (l >> 4) + 4 * r;
-                if (row < n && col < n) {
-                    double* p = g.C + row * n + col;
-                    *p = g.accumulate ? *p + acc[i][j][r] : acc[i][j][r];
-                }
-            }
+    tile_zero(acc);
+    const long kbeg = g.b_upper_nt ? c0 : 0;
+    if (g.nt1) tile_product<true>(g.A1, n, n, g.B1, n, n, n, kbeg, g.alpha1, r0, c0, acc, sA, sB, tid);  // (uniform branch)
+    else tile_product<false>(g.A1, n, n, g.B1, n, n, n, kbeg, g.alpha1, r0, c0, acc, sA, sB, tid);
+    if (g.A2) tile_product<true>(g.A2, n, n, g.B2, n, n, n, 0, g.alpha2, r0, c0, acc, sA, sB, tid);
+    tile_each(acc, r0, c0, tid, [&](long row, long col, double v) {
+        if (row < n && col < n) {
+            double* p = g.C + row * n + col;
+            *p = g.accumulate ? *p + v : v;
         }
+    });
 }
 
 // upper half of P from its lower half (32 x 32 tiles through LDS) and var = diag(P)

@@ -324,6 +324,23 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                                          diffusion_squared_local=sig[-1] if sig else [])
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
 
+    # ------------------------------------------------------------------ backward walks (smoothing, joint draws)
+    def _walk_inputs(self, who, solution):
+        """What `smooth`, `sample` and `sample_dense` walk backwards: (the device-resident states of `solution`, the one filter
+        that owns them).  Refuses every solver but the fp64 covariance-form ones of pnmol.white."""
+        from . import latent, sqrtform
+
+        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
+            raise TypeError(f"{who}() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+        ys = list(solution._ys)
+        if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
+            raise TypeError(f"{who}() needs the device-resident states of this package's solve()")
+        flt = ys[-1].device_state.filter
+        if any(y.device_state.filter is not flt for y in ys):
+            raise ValueError(f"{who}(): the states of the solution belong to different device filters")
+        return ys, flt
+
     # ------------------------------------------------------------------ smoothing
     def smooth(self, solution, dense="marginal"):
         """Rauch-Tung-Striebel smoothing of a `solve()` result (kalman.py:33-46 of the reference, covariance form).
@@ -338,19 +355,9 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         the smoothed states are bit for bit those of dense=None.  "full": the bridges also keep the lag-one cross-covariance
         C_k, T (n d)^2 more doubles on the device in all (as much as the states themselves), for `state_at`.  None: nothing.
         Supported: fp64 white-noise solvers (pnmol.white), constant and adaptive steps."""
-        from . import latent, sqrtform
-
         if dense not in (None, "marginal", "full"):
             raise ValueError(f'smooth(): dense must be None, "marginal" or "full", got {dense!r}')
-        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
-            raise TypeError(f"smooth() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
-                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
-        ys = list(solution._ys)
-        if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
-            raise TypeError("smooth() needs the device-resident states of this package's solve()")
-        flt = ys[-1].device_state.filter
-        if any(y.device_state.filter is not flt for y in ys):
-            raise ValueError("smooth(): the states of the solution belong to different device filters")
+        ys, flt = self._walk_inputs("smooth", solution)
         t = np.asarray(solution.t)
         nxt = ys[-1].device_state.clone()                       # terminal state: the filtered one
         out = [rv.DeviceMultivariateNormal(np.array(ys[-1].mean), nxt)]
@@ -383,11 +390,6 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         standard normals, `noise[k]` of shape (S, 2D) for k < T and (S, D) for k = T (D = n d).  calibrated=True draws from
         the calibrated posterior (noise scale sqrt(solution.diffusion_squared_calibrated)).  `solution` is unchanged.
         Supported: fp64 white-noise solvers (pnmol.white), constant and adaptive steps."""
-        from . import latent, sqrtform
-
-        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
-            raise TypeError(f"sample() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
-                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
         return self._sample_walk("sample", solution, num_samples, seed, noise, calibrated)[0]
 
     def sample_dense(self, solution, num_samples, ts, *, seed=0, noise=None, noise_dense=None, calibrated=False):
@@ -413,17 +415,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         return self._sample_walk("sample_dense", solution, num_samples, seed, noise, calibrated, ts, noise_dense)
 
     def _sample_walk(self, who, solution, num_samples, seed, noise, calibrated, ts=None, noise_dense=None):
-        from . import latent, sqrtform
-
-        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
-            raise TypeError(f"{who}() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
-                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
-        ys = list(solution._ys)
-        if not ys or not all(isinstance(y, rv.DeviceMultivariateNormal) for y in ys):
-            raise TypeError(f"{who}() needs the device-resident states of this package's solve()")
-        flt = ys[-1].device_state.filter
-        if any(y.device_state.filter is not flt for y in ys):
-            raise ValueError(f"{who}(): the states of the solution belong to different device filters")
+        ys, flt = self._walk_inputs(who, solution)
         S, T = int(num_samples), len(ys) - 1
         if S < 1:
             raise ValueError(f"{who}(): num_samples must be at least 1, got {num_samples}")

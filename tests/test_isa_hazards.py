@@ -3,9 +3,14 @@
 hipcc (ROCm 7.2) normally separates an MFMA from a VALU / LDS read of its accumulator by `s_nop`s.  Twice in this repository
 it put them BEHIND the first reads, where an MFMA chain ended a conditional block (DESIGN.md section 3a''): accumulator
 element 3 -- rows fk + 12 of a tile -- came out stale, only in builds without the timeline stamps.  The kernels carry
-hand-written wait states there (`mfma_result_guard`); `tools/mfma_hazard_scan.py` walks the assembly (through branches)
-and this test keeps it clean, and checks that the scanner does see the hazard when the guard is compiled out."""
+hand-written wait states there (`mfma_result_guard`; `tile_product` of csrc/pnmol_tile.hpp); `tools/mfma_hazard_scan.py`
+walks the assembly (through branches) and this test keeps every translation unit clean, and checks that the scanner does see
+the hazard in a recorded shape.  Per translation unit it also checks what the file promises about its own ISA: the products
+of the smoother, the sampler and the measurement update really run on the fp64 MFMA; the dense output (element-wise and
+memory-bound) holds no MFMA at all and fits its registers -- in the full-covariance kernel a lane holds an n x n block of
+double2 accumulators, and a spill would show up here before any run."""
 import pathlib
+import re
 import shutil
 import subprocess
 import sys
@@ -24,16 +29,29 @@ def _scan(src, tmp_path, *defines):
     res = subprocess.run([sys.executable, str(ROOT / "tools" / "mfma_hazard_scan.py"), str(out), "10"],
                          check=True, capture_output=True, text=True).stdout
     _scan.sc1x2 = int(res.strip().splitlines()[-2].split()[0])     # "N 8-byte sc1 loads" (second check of the scanner)
+    _scan.isa = out.read_text()
     return int(res.strip().splitlines()[-1].split()[0]), res
 
 
+FP64_MFMA = ("pnmol_smooth.hip", "pnmol_sample.hip", "pnmol_observe.hip")
+
+
 @pytest.mark.skipif(not pathlib.Path(HIPCC).exists(), reason="hipcc not available")
-@pytest.mark.parametrize("name", ["pnmol_hip.hip", "pnmol_sqrt.hip"])
+@pytest.mark.parametrize("name", sorted(p.name for p in CSRC.glob("*.hip")))      # (every translation unit of the library)
 def test_no_mfma_result_is_read_too_early(tmp_path, name):
     hits, report = _scan(CSRC / name, tmp_path)
     assert hits == 0, report
     # hand-over data is never read with 8-byte sc1 loads (they were served stale L2 lines: DESIGN.md section 3a'')
     assert _scan.sc1x2 == 0, report
+    isa = _scan.isa
+    if name in FP64_MFMA:
+        assert "v_mfma_f64_16x16x4" in isa                      # (the products really run on the fp64 MFMA)
+    if name == "pnmol_dense.hip":
+        assert "v_mfma" not in isa
+        # every kernel of the file, the n = 4 instantiation of k_dn_state included: no scratch memory
+        sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", isa)
+        assert len(sizes) >= 18 and all(int(s) == 0 for s in sizes), sizes
+        assert "k_dn_stateILi4E" in isa
 
 
 SYNTHETIC = """
