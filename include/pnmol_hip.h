@@ -134,6 +134,37 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dds, const double
  * graphs are dropped only if the width changes).  -1 if a row of L has no diagonal entry. */
 int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, const double* shift_d);
 
+/* Pointwise reaction terms evaluated on the device --------------------------------------------------------------------------
+ * For u_t = L u + r(u) with r(u) = P(u) + A(u) / B(u), the same at every mesh point: P, A, B polynomials with scalar
+ * coefficients in ascending powers, degree <= PNMOL_REACTION_MAXDEG (a degree of -1: the term is absent; A and B together or
+ * not at all).  Logistic / Fisher-KPP, Allen-Cahn, Nagumo and the spruce-budworm rational term have this form.  No reference
+ * counterpart (its f is a callable); the arithmetic is that of `pnmol_filter_predict_mean` + `pnmol_filter_set_operator_diagonal`
+ * with jdiag = r'(u), shift = r'(u) u - r(u) at the predicted mean u, r and r' = P' + (A' B - A B') / B^2 by Horner, every
+ * operation rounded on its own.
+ * `pnmol_filter_set_reaction` (NULL clears) stores the descriptor, restores the stencil rows of the L given at creation and a
+ * zero shift, forgets the error model and drops captured graphs.  -1 (reason in `pnmol_last_error`): null filter, latent-force
+ * filter (d_state != d), fp32 filter, a row of L without a diagonal entry, a degree outside [-1, 7], A without B or B without A,
+ * a coefficient that is not finite, B identically zero.  While a reaction is set
+ *   - `pnmol_filter_set_operator` and `pnmol_filter_set_operator_diagonal` return -1 (clear the reaction first);
+ *   - every step of `pnmol_filter_steps(_begin)` is re-linearised on the device at its own predicted mean, so the constant-step
+ *     loop runs semilinear problems without a host round trip.  The loop then takes self-contained steps (the next step's
+ *     innovation is no longer prepared inside the previous step's read-out launch, which would precede the re-linearisation)
+ *     and carries no error model: `error_sigma2` of its steps is NaN, and an error model prepared before is forgotten;
+ *   - `pnmol_filter_step` is unchanged: it uses the operator that is set.  For one step call, in this order,
+ *     `pnmol_filter_linearize(f, in, dt)` (enqueues the re-linearisation for a step from `in` over dt: no synchronisation, no
+ *     read-back), `pnmol_filter_prepare_error_model(f, dt)` (if the error estimate is wanted: it reads the new operator) and
+ *     `pnmol_filter_step(f, in, dt, ...)`.  -1: null argument, foreign state, dt <= 0, no reaction set.
+ * A non-finite r(u) (a pole of A / B at a predicted value) is not trapped: it reaches the factorisation as a NaN pivot and the
+ * step returns -3, as for any other innovation matrix that is not positive definite.
+ * After `pnmol_filter_set_reaction(f, NULL)` the filter behaves bit for bit like one that never had a reaction. */
+#define PNMOL_REACTION_MAXDEG 7
+typedef struct pnmol_reaction {
+    int deg_p, deg_a, deg_b; /* -1: term absent */
+    double p[PNMOL_REACTION_MAXDEG + 1], a[PNMOL_REACTION_MAXDEG + 1], b[PNMOL_REACTION_MAXDEG + 1];
+} pnmol_reaction;
+int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r);
+int pnmol_filter_linearize(pnmol_filter* f, const pnmol_state* in, double dt);
+
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);
 int pnmol_state_destroy(pnmol_state* s); /* -1 for the target of an unfinished pnmol_filter_steps_begin */

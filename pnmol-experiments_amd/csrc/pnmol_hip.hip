@@ -3456,7 +3456,11 @@ void drop_graphs(pnmol_filter* f);
 // the full predict and STEADY steps only run k_predict's vector workgroup; both write P only in the call's last step.
 enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 
-inline bool fused_loop(const pnmol_filter* f) { return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0; }
+// The loop is not fused while a reaction is set: the fused loop makes the next step's z and G inside the previous step's
+// k_readout launch, before that step's re-linearisation could run.
+inline bool fused_loop(const pnmol_filter* f) {
+    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !f->has_reaction;
+}
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
 // the left-looking one otherwise (PNMOL_HIP_SWEEP_RL=0 forces it, for A/B runs)
@@ -3633,6 +3637,16 @@ int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double 
     return -1;
 }
 
+// a step of the constant-step loop: with a reaction set the operator is re-linearised at this step's predicted mean first
+// (k_linearize, pnmol_reaction.hip)
+int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
+              double* varout, StepKind kind) {
+    if (f->has_reaction) {
+        if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt)) return rc;
+    }
+    return dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind);
+}
+
 void drop_graphs(pnmol_filter* f) {
     for (auto& g : f->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -3657,8 +3671,8 @@ int get_graph(pnmol_filter* f, double* P0, double* M0, double* P1, double* M1, d
     HIPCHK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     int rc = 0;
     for (int it = 0; it < nsteps && rc == 0; ++it)
-        rc = (it & 1) ? dispatch_step(f, P1, M1, dt, dt, P0, M0, var, true, fused_loop(f) ? STEP_STEADY : STEP_FULL)
-                      : dispatch_step(f, P0, M0, dt, dt, P1, M1, var, true, fused_loop(f) ? STEP_STEADY : STEP_FULL);
+        rc = (it & 1) ? loop_step(f, P1, M1, dt, dt, P0, M0, var, fused_loop(f) ? STEP_STEADY : STEP_FULL)
+                      : loop_step(f, P0, M0, dt, dt, P1, M1, var, fused_loop(f) ? STEP_STEADY : STEP_FULL);
     hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
     if (rc != 0 || e != hipSuccess) {
         if (graph) (void)hipGraphDestroy(graph);
@@ -3808,6 +3822,8 @@ int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
 }
 
 }  // namespace
+
+void pnmol_drop_graphs(pnmol_filter* f) { drop_graphs(f); }
 
 // ---- the sweep workspace of the callers outside the filter step (pnmol_internal.hpp) ---------------------------------------
 hipError_t sweep_ws_alloc(SweepWs* w, pnmol_ctx* ctx, int rt, int cb) {
@@ -4351,6 +4367,10 @@ int pnmol_filter_prepare_error_model(pnmol_filter* f, double dt) {
 int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double* shift_d) {
     if (!f || !M_dd) return -1;
     pnmol_ctx* ctx = f->ctx;
+    if (f->has_reaction) {
+        ctx->err = "pnmol_filter_set_operator: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
+        return -1;
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<int> ecol;
     std::vector<double> eval;
@@ -4378,6 +4398,10 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
 int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, const double* shift_d) {
     if (!f || !jdiag_d) return -1;
     pnmol_ctx* ctx = f->ctx;
+    if (f->has_reaction) {
+        ctx->err = "pnmol_filter_set_operator_diagonal: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
+        return -1;
+    }
     if (!f->base_has_diag) {
         ctx->err = "pnmol_filter_set_operator_diagonal: a row of the operator given at creation has no diagonal entry";
         return -1;
@@ -4739,6 +4763,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     if (rc != 0) return rc;
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
+    if (f->has_reaction) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
     double frame = s->frame_dt;
@@ -4766,8 +4791,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
             it += 2;
             continue;
         }
-        rc = dispatch_step(f, curP, curM, frame, dt, nxtP, nxtM, s->var, true,
-                           !fused ? STEP_FULL : (it == 0 ? STEP_FIRST : STEP_STEADY));
+        rc = loop_step(f, curP, curM, frame, dt, nxtP, nxtM, s->var, !fused ? STEP_FULL : (it == 0 ? STEP_FIRST : STEP_STEADY));
         if (rc != 0) return rc;
         double* t;
         t = curP, curP = nxtP, nxtP = t;

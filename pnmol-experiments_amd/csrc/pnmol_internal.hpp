@@ -170,6 +170,10 @@ struct pnmol_filter {
     struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
     // Measurement updates (pnmol_state_observe): one workspace per padded column count, allocated on first use
     std::vector<ObserveWs*> ob_ws;
+    // Pointwise reaction term evaluated on the device (pnmol_filter_set_reaction; pnmol_reaction.hip).  While one is set the
+    // constant-step loop re-linearises in front of every step, runs non-fused and carries no error model.
+    bool has_reaction = false;
+    pnmol_reaction reaction{};
 };
 
 struct pnmol_state {
@@ -245,6 +249,13 @@ void pnmol_dense_free_ws(pnmol_filter* f);
 void pnmol_observe_free_ws(pnmol_filter* f);
 // pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
+
+// pnmol_reaction.hip: enqueue k_linearize on the ctx stream for one step over dt from the mean `mean` (Dp, in the frame
+// frame_dt; 0 = raw coordinates): the diagonal slots of ell_val and the shift become those of the EK1 linearisation of
+// f->reaction at the predicted mean.  Needs f->has_reaction; no synchronisation.  -2: the launch failed.
+int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt);
+// pnmol_hip.hip: destroy the captured graphs of the constant-step loop
+void pnmol_drop_graphs(pnmol_filter* f);
 
 // The RTS smoother step (pnmol_smoother_step; pnmol_smooth.hip).
 constexpr int SM_MAXN = 4;

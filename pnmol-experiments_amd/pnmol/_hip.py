@@ -74,6 +74,8 @@ SYMBOLS = {
     "pnmol_filter_predict_mean": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _c_double_p]),
     "pnmol_filter_set_operator": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pnmol_filter_set_operator_diagonal": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
+    "pnmol_filter_set_reaction": (ctypes.c_int, [_vp, _vp]),           # (pnmol_reaction*: pde/reactions.py, ReactionDesc)
+    "pnmol_filter_linearize": (ctypes.c_int, [_vp, _vp, ctypes.c_double]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
     "pnmol_state_clone": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
@@ -304,6 +306,7 @@ class Filter:
         self.handle = h
         self.d, self.n, self.nB, self.m = d, int(num_derivatives) + 1, nB, d + nB
         self.error_model_dt = None
+        self.reaction = None        # the pde.reactions.Reaction the device evaluates (`set_reaction`)
         # raw handles of the live pnmol_state objects of this filter, keyed by id(State): the C ABI refuses to destroy a
         # filter that still has states (include/pnmol_hip.h, "Lifetimes").  A plain dict, not weak references: the
         # cyclic collector clears weakrefs to unreachable objects BEFORE it runs finalisers, so a WeakSet would be empty
@@ -381,6 +384,21 @@ class Filter:
                        "pnmol_filter_set_operator_diagonal")
         self.error_model_dt = None
 
+    def set_reaction(self, reaction):
+        """A pointwise reaction term (pde/reactions.py) that the device linearises itself, or None to clear it:
+        `pnmol_filter_set_reaction`.  While one is set, `steps` re-linearises in front of every step."""
+        desc = None if reaction is None else reaction.to_ctypes()
+        self.ctx.check(self.lib.pnmol_filter_set_reaction(self.handle, None if desc is None else ctypes.byref(desc)),
+                       "pnmol_filter_set_reaction")
+        self.reaction = reaction
+        self.error_model_dt = None
+
+    def linearize(self, state_in, dt):
+        """Enqueue the EK1 linearisation of the reaction at the predicted mean of a step from `state_in` over dt
+        (`pnmol_filter_linearize`; no synchronisation).  Then `prepare_error_model(dt)`, then `step(state_in, dt)`."""
+        self.ctx.check(self.lib.pnmol_filter_linearize(self.handle, state_in.handle, float(dt)), "pnmol_filter_linearize")
+        self.error_model_dt = None
+
     def step(self, state_in, dt, want_error=True):
         out = State(self)
         info = StepOut()
@@ -448,11 +466,15 @@ class Filter:
         rc = self.lib.pnmol_filter_steps(self.handle, state.handle, int(k), float(dt),
                                          _dp(means) if want_means else None, _dp(stds) if want_stds else None, infos)
         self.ctx.check(rc, "pnmol_filter_steps")
+        if self.reaction is not None:
+            self.error_model_dt = None      # (the loop re-linearises: an error model prepared before is forgotten)
         return means, stds, infos
 
     def steps_begin(self, state, k, dt):
         self.ctx.check(self.lib.pnmol_filter_steps_begin(self.handle, state.handle, int(k), float(dt)),
                        "pnmol_filter_steps_begin")
+        if self.reaction is not None:
+            self.error_model_dt = None      # (the loop re-linearises: an error model prepared before is forgotten)
         self._pending_k = int(k)
 
     def steps_end(self, state, want_means=True, want_stds=True):

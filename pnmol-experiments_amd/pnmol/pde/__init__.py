@@ -1,3 +1,3 @@
 """PDE problems (reference: src/pnmol/pde/__init__.py)."""
 
-from . import examples, mixins, problems  # noqa: F401
+from . import examples, mixins, problems, reactions  # noqa: F401

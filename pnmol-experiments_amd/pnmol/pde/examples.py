@@ -177,6 +177,32 @@ def spruce_budworm_1d(*, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=0.1, y0_fu
                f=f_spruce, df=df_spruce, df_diagonal=df_diagonal_spruce)
 
 
+def reaction_diffusion_1d_discretized(reaction, *, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=1.0, y0_fun=None, dx=0.1,
+                                      kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
+                                      stencil_size_boundary=3, bcond="dirichlet"):
+    """u_t = kappa u_xx + r(u) for a pointwise `reaction` (pde/reactions.py), discretised like the spruce-budworm recipe
+    above: the same problem class, with f, df and df_diagonal taken from the reaction.  `pde.reaction` lets the solver
+    evaluate r on the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`)."""
+    if bbox is None:
+        bbox = [0.0, 1.0]
+    bbox = np.asarray(bbox, dtype=np.float64)
+    if y0_fun is None:
+        y0_fun = sin_bell_1d
+    cls = {"dirichlet": problems.SemiLinearEvolutionDirichlet, "neumann": problems.SemiLinearEvolutionNeumann}.get(bcond)
+    if cls is None:
+        raise ValueError
+    f, df, df_diagonal = reaction.callables()
+    pde = cls(t0=t0, tmax=tmax, y0_fun=y0_fun, bbox=bbox, diffop=diffops.laplace(), diffop_scale=diffusion_rate,
+              f=f, df=df, df_diagonal=df_diagonal)
+    pde.reaction = reaction
+    mesh_spatial = mesh.RectangularMesh.from_bbox_1d(pde.bbox, step=dx)
+    if kernel is None:
+        kernel = kernels.SquareExponential()
+    pde.discretize(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
+                   stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
+    return pde
+
+
 # Initial-condition defaults; they adhere to Dirichlet conditions (examples.py:344-357)
 
 

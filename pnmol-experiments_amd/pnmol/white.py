@@ -75,6 +75,12 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         self._device_pde = pde
         self._gram = gram
         self._error_models = {}
+        if self._reaction_for_device(pde) is not None:
+            self._device_filter.set_reaction(pde.reaction)
+
+    def _reaction_for_device(self, pde):
+        """The reaction term the device evaluates itself for this solver and problem, or None (host callables)."""
+        return None
 
     # True: the reference's own two `update_sqrt` calls, on the device (below); False: closed form on the host (O(d^3) LAPACK);
     # None (default; PNMOL_INIT_ON_DEVICE=0/1 overrides): on the device from n d >= 4096 on, where the host form takes
@@ -235,7 +241,12 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
     def attempt_step(self, state, dt, pde):
         """One predict + update + calibrate step on the GPU (white.py:96-146); `state` is not modified."""
         dev_in = self._device_state_of(state, pde)
-        if self.semilinear:
+        if self.semilinear and self._device_filter.reaction is not None:
+            # pointwise reaction described to the device (pde/reactions.py): linearised there at the predicted mean, nothing
+            # comes back and nothing goes up
+            self._device_filter.linearize(dev_in, dt)
+            self._device_filter.prepare_error_model(dt)
+        elif self.semilinear:
             # EK1 linearisation at the predicted mean (white.py:192-208): f and df are host callables, so the
             # predicted point comes back once per step; the new stencil rows and shift go to the device
             flt = self._device_filter
@@ -297,6 +308,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             raise TypeError("solve_marginals needs the Constant step rule")
         state = self.initialize(pde)
         dev = state.y.device_state
+        on_device = self._device_filter.reaction is not None    # re-linearised inside the loop; no error model there
         dt0 = self.steprule.first_dt(pde)
         ts, dts, t, dt = [pde.t0], [], pde.t0, dt0
         while t < pde.tmax and (num_steps is None or len(dts) < num_steps):
@@ -313,7 +325,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             j = i
             while j < len(dts) and dts[j] == dts[i]:
                 j += 1
-            self._ensure_error_model(pde, dts[i])
+            if not on_device:
+                self._ensure_error_model(pde, dts[i])
             mk, sk, infos = self._device_filter.steps(dev, j - i, dts[i])
             means.extend(mk), stds.extend(sk)
             sig.extend(o.diffusion_squared_local for o in infos)
@@ -493,5 +506,21 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return None
         return np.asarray(dfd(t, m_at), dtype=np.float64)
 
+    # A problem with a `reaction` attribute (pde/reactions.py; `pde.examples.reaction_diffusion_1d_discretized`) is linearised on
+    # the device: `attempt_step` takes no host round trip and `solve_marginals` runs.  False: the host callables, as for
+    # every other semilinear problem.  fp64 covariance-form white-noise solvers only; the others use the callables.
+    reaction_on_device = True
+
+    def _reaction_for_device(self, pde):
+        from . import sqrtform
+
+        reaction = getattr(pde, "reaction", None)
+        if (reaction is None or not self.reaction_on_device or self.dtype != "f64"
+                or isinstance(self, sqrtform._SqrtFormMixin)):
+            return None
+        return reaction
+
     def solve_marginals(self, pde, *, num_steps=None):
-        raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
+        if self._reaction_for_device(pde) is None:
+            raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
+        return super().solve_marginals(pde, num_steps=num_steps)
