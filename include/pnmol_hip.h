@@ -165,6 +165,37 @@ typedef struct pnmol_reaction {
 int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r);
 int pnmol_filter_linearize(pnmol_filter* f, const pnmol_state* in, double dt);
 
+/* Coupled pointwise reactions (systems) --------------------------------------------------------------------------------------
+ * For a state [u_0; ...; u_{C-1}] of C species on the same N mesh points (d = C N, species-major) and
+ * r_c(u) = P_c(u) + A_c(u) / B_c(u) with u = (u_0 .. u_{C-1}) at ONE mesh point: P_c, A_c, B_c polynomials in the C species, each a
+ * sum of at most PNMOL_SYSTEM_MAXTERMS monomials coef * u_0^pow[0] * ... (exponents 0..7; a polynomial of 0 terms is zero; A_c and
+ * B_c together or not at all).  Lotka-Volterra, SIR (-+beta s i / (s + i + r)) and Gray-Scott have this form.  The Jacobian has C
+ * entries per row, at the same mesh point in every species block: row c N + j of M = L + J holds J_ck at column k N + j.
+ * `pnmol_filter_set_reaction_system` (NULL clears) mirrors `pnmol_filter_set_reaction`: it stores the descriptor, installs the
+ * widened image of the L given at creation -- every PDE row gets a slot for each of its C same-point columns (value 0 where L has
+ * none), slots in ascending column order, width at most that of L plus C - 1 -- with a zero shift, forgets the error model and
+ * drops captured graphs.  A filter holds one reaction of either kind: each setter replaces what the other had set, NULL to either
+ * clears either, and the cleared filter behaves bit for bit like one that never had a reaction.  While a system is set the operator
+ * calls are refused, `pnmol_filter_linearize` and `pnmol_filter_steps(_begin)` re-linearise as above.
+ * Arithmetic (every operation rounded on its own; pnmol/pde/reactions.py, `SystemReaction`, is the same on the host): u_k as in
+ * `pnmol_filter_predict_mean`; a monomial starts from coef and is multiplied by u_0 pow[0] times, then by u_1 pow[1] times, ...;
+ * a polynomial is the sum of its monomials in the order given, starting from the first; the partial derivative of a monomial by
+ * u_k with exponent e >= 1 starts from e * coef and takes the same multiplications with one factor u_k fewer (e = 0: the monomial
+ * is skipped); J_ck = dP_k + (dA_k B - A dB_k) / (B B), r_c = P + A / B, shift_i = ((J_c0 u_0 + J_c1 u_1) + ...) - r_c.
+ * -1 (reason in `pnmol_last_error`): null filter, ncomp outside [1, 4], d not a multiple of ncomp, a term count outside [0, 8], an
+ * exponent outside [0, 7] or a non-zero exponent of a species >= ncomp, A_c without B_c or B_c without A_c, a coefficient that is
+ * not finite, a B_c whose coefficients are all zero, latent-force filter, fp32 filter, a row of L without a diagonal entry.
+ * A pole of A_c / B_c is not trapped: the step returns -3. */
+#define PNMOL_SYSTEM_MAXCOMP  4
+#define PNMOL_SYSTEM_MAXTERMS 8
+typedef struct pnmol_monomial    { double coef; int pow[PNMOL_SYSTEM_MAXCOMP]; } pnmol_monomial;
+typedef struct pnmol_system_poly { int nterms; pnmol_monomial term[PNMOL_SYSTEM_MAXTERMS]; } pnmol_system_poly; /* 0 terms: zero */
+typedef struct pnmol_reaction_system {
+    int ncomp;                                     /* C in 1..4; the state is [u_0; ...; u_{C-1}], d = C * N */
+    pnmol_system_poly p[PNMOL_SYSTEM_MAXCOMP], a[PNMOL_SYSTEM_MAXCOMP], b[PNMOL_SYSTEM_MAXCOMP];
+} pnmol_reaction_system;                           /* r_c(u) = P_c(u) + A_c(u) / B_c(u), u = (u_0..u_{C-1}) at ONE mesh point */
+int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_system* r);   /* NULL clears */
+
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);
 int pnmol_state_destroy(pnmol_state* s); /* -1 for the target of an unfinished pnmol_filter_steps_begin */

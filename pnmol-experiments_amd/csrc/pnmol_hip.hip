@@ -4281,6 +4281,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_sample_free_ws(f);
     pnmol_dense_free_ws(f);
     pnmol_observe_free_ws(f);
+    pnmol_reaction_free_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;

@@ -174,6 +174,15 @@ struct pnmol_filter {
     // constant-step loop re-linearises in front of every step, runs non-fused and carries no error model.
     bool has_reaction = false;
     pnmol_reaction reaction{};
+    // ... or a coupled system of sys.ncomp species (pnmol_filter_set_reaction_system), has_reaction with sys_set: the widened
+    // image of the creation-time operator (every PDE row has a slot for each of its ncomp same-point columns; sys_w wide, built
+    // for sys_img_ncomp species, 0 = none yet) and the (ncomp, mp) table of those slots
+    bool sys_set = false;
+    pnmol_reaction_system sys{};
+    int* sys_col = nullptr;
+    double* sys_val = nullptr;
+    int* sys_slot = nullptr;
+    int sys_w = 0, sys_img_ncomp = 0;
 };
 
 struct pnmol_state {
@@ -250,9 +259,11 @@ void pnmol_observe_free_ws(pnmol_filter* f);
 // pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
 
-// pnmol_reaction.hip: enqueue k_linearize on the ctx stream for one step over dt from the mean `mean` (Dp, in the frame
-// frame_dt; 0 = raw coordinates): the diagonal slots of ell_val and the shift become those of the EK1 linearisation of
-// f->reaction at the predicted mean.  Needs f->has_reaction; no synchronisation.  -2: the launch failed.
+void pnmol_reaction_free_ws(pnmol_filter* f);
+// pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system) on the ctx stream for one step over dt from
+// the mean `mean` (Dp, in the frame frame_dt; 0 = raw coordinates): the diagonal (same-point) slots of ell_val and the shift
+// become those of the EK1 linearisation of the reaction at the predicted mean.  Needs f->has_reaction; no synchronisation.
+// -2: the launch failed.
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);

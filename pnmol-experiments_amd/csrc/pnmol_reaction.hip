@@ -7,6 +7,10 @@
 // Horner and patches the diagonal slots of the stencil rows and the shift, as k_operator_diagonal does from a host buffer.
 // Nothing crosses the bus, so the constant-step loop re-linearises in front of every step (launch_step's callers in
 // pnmol_hip.hip) and stays on the device.
+//
+// Coupled systems of C <= 4 species (`pnmol_filter_set_reaction_system`; Lotka-Volterra, SIR): r_c depends on all species at the
+// same mesh point, so row c N + j of the Jacobian has C entries, at the columns k N + j.  The setter widens the stencil image
+// of L by those columns once (build_system_image), and k_linearize_system patches the C same-point slots of every row.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -64,6 +68,117 @@ __global__ __launch_bounds__(256) void k_linearize(LinearizeArgs a, int n, const
     shift[i] = dr * u - r;
 }
 
+// ---- coupled systems: r_c(u) = P_c(u) + A_c(u) / B_c(u) of the C species at one mesh point (pnmol_filter_set_reaction_system)
+struct LinearizeSystemArgs {
+    pnmol_reaction_system r;
+    double c[MAXN];  // as in LinearizeArgs
+    double s0;
+};
+
+constexpr int SC = PNMOL_SYSTEM_MAXCOMP;
+
+// coef * u_0^pw[0] * u_1^pw[1] * ..., one multiplication at a time, species by species; `less` takes one factor off that species
+__device__ __forceinline__ double monomial(double start, const int (&pw)[SC], int less, const double (&u)[SC]) {
+#pragma clang fp contract(off)
+    double m = start;
+#pragma unroll
+    for (int k = 0; k < SC; ++k) {
+        const int cnt = pw[k] - (k == less ? 1 : 0);
+        for (int e = 0; e < cnt; ++e) m = m * u[k];
+    }
+    return m;
+}
+
+// value and the SC partial derivatives of a polynomial: the sum of its terms in the order given, starting from the first one
+// (a term whose exponent of u_k is 0 is no term of the k-th derivative).  The descriptor sits in the kernel-argument segment and
+// every index into it is uniform across the wave; u and the sums stay in registers (all loops over species are unrolled).
+__device__ __forceinline__ void poly_eval(const pnmol_system_poly& p, const double (&u)[SC], double& v, double (&dv)[SC]) {
+#pragma clang fp contract(off)
+    v = 0.0;
+#pragma unroll
+    for (int k = 0; k < SC; ++k) dv[k] = 0.0;
+    bool first = true, dfirst[SC];
+#pragma unroll
+    for (int k = 0; k < SC; ++k) dfirst[k] = true;
+    for (int t = 0; t < p.nterms; ++t) {
+        const double coef = p.term[t].coef;
+        int pw[SC];
+#pragma unroll
+        for (int k = 0; k < SC; ++k) pw[k] = p.term[t].pow[k];
+        const double m = monomial(coef, pw, -1, u);
+        v = first ? m : v + m;
+        first = false;
+#pragma unroll
+        for (int k = 0; k < SC; ++k) {
+            if (pw[k] >= 1) {
+                const double dm = monomial(pw[k] * coef, pw, k, u);
+                dv[k] = dfirst[k] ? dm : dv[k] + dm;
+                dfirst[k] = false;
+            }
+        }
+    }
+}
+
+// One thread per measurement row i = c N + j: the C species at point j, r_c and its C partial derivatives, the C same-point slots
+// of the row and its shift.  Every operation is rounded on its own, in the order of SystemReaction (pnmol/pde/reactions.py).
+__global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a, int n, int N, const double* __restrict__ mean,
+                                                          double* __restrict__ ell_val, const double* __restrict__ base_val,
+                                                          const int* __restrict__ slot, double* __restrict__ shift, int d,
+                                                          int dp, int mp) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= mp) return;
+    if (i >= d) {
+        shift[i] = 0.0;
+        return;
+    }
+    const int C = a.r.ncomp;
+    const int c = i / N, j = i - c * N;
+    double u[SC];
+#pragma unroll
+    for (int k = 0; k < SC; ++k) {
+        u[k] = 0.0;
+        if (k < C) {
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = acc + a.c[q] * mean[(long)q * dp + (long)k * N + j];
+            u[k] = a.s0 * acc;
+        }
+    }
+    double r = 0.0, J[SC];
+#pragma unroll
+    for (int k = 0; k < SC; ++k) J[k] = 0.0;
+    // the component is uniform across a wave except where a wave straddles two species blocks: the descriptor is indexed by the
+    // loop counter, never by the thread's own c
+#pragma unroll
+    for (int cc = 0; cc < SC; ++cc) {
+        if (cc == c) {
+            double P, dP[SC];
+            poly_eval(a.r.p[cc], u, P, dP);
+            r = P;
+#pragma unroll
+            for (int k = 0; k < SC; ++k) J[k] = dP[k];
+            if (a.r.a[cc].nterms > 0) {
+                double A, dA[SC], B, dB[SC];
+                poly_eval(a.r.a[cc], u, A, dA);
+                poly_eval(a.r.b[cc], u, B, dB);
+                r = P + A / B;
+#pragma unroll
+                for (int k = 0; k < SC; ++k) J[k] = dP[k] + (dA[k] * B - A * dB[k]) / (B * B);
+            }
+        }
+    }
+    double Ju = J[0] * u[0];
+#pragma unroll
+    for (int k = 0; k < SC; ++k) {
+        if (k < C) {
+            const long e = (long)slot[(long)k * mp + i] * mp + i;
+            ell_val[e] = base_val[e] - J[k];
+            if (k >= 1) Ju = Ju + J[k] * u[k];
+        }
+    }
+    shift[i] = Ju - r;
+}
+
 // the stencil rows of the operator given at creation and a zero shift (what pnmol_filter_set_operator_diagonal restores
 // after a dense upload), on the ctx stream
 int restore_base_operator(pnmol_filter* f) {
@@ -85,19 +200,115 @@ bool all_finite(const double* c, int deg) {
     return true;
 }
 
+// why a system descriptor is refused, or nullptr
+const char* system_descriptor_fault(const pnmol_reaction_system* r) {
+    if (r->ncomp < 1 || r->ncomp > PNMOL_SYSTEM_MAXCOMP) return "ncomp outside [1, 4]";
+    for (int c = 0; c < r->ncomp; ++c) {
+        const pnmol_system_poly* polys[3] = {&r->p[c], &r->a[c], &r->b[c]};
+        for (const pnmol_system_poly* p : polys)
+            if (p->nterms < 0 || p->nterms > PNMOL_SYSTEM_MAXTERMS) return "a term count outside [0, 8]";
+        for (const pnmol_system_poly* p : polys)
+            for (int t = 0; t < p->nterms; ++t)
+                for (int k = 0; k < PNMOL_SYSTEM_MAXCOMP; ++k) {
+                    if (p->term[t].pow[k] < 0 || p->term[t].pow[k] > 7) return "an exponent outside [0, 7]";
+                    if (k >= r->ncomp && p->term[t].pow[k] != 0) return "a non-zero exponent of a species >= ncomp";
+                }
+        if ((r->a[c].nterms > 0) != (r->b[c].nterms > 0))
+            return "the numerator a[c] and the denominator b[c] are given together or not at all";
+        for (const pnmol_system_poly* p : polys)
+            for (int t = 0; t < p->nterms; ++t)
+                if (!std::isfinite(p->term[t].coef)) return "a coefficient is not finite";
+        if (r->b[c].nterms > 0) {
+            bool zero = true;
+            for (int t = 0; t < r->b[c].nterms; ++t) zero = zero && r->b[c].term[t].coef == 0.0;
+            if (zero) return "a denominator b[c] is identically zero";
+        }
+    }
+    return nullptr;
+}
+
+// The widened image of the operator given at creation for C species: every PDE row i = c N + j has a slot for each column
+// k N + j (the value of L there, or 0), slots in ascending column order as build_ell leaves them; boundary rows as they are.
+// Built on the host from the base image (read back once per C) and kept on the device beside the (C, mp) slot table.
+int build_system_image(pnmol_filter* f, int C) {
+    pnmol_ctx* ctx = f->ctx;
+    const int d = f->d, mp = f->mp, bw = f->base_w, N = d / C;
+    std::vector<int> bcol((size_t)bw * mp);
+    std::vector<double> bval((size_t)bw * mp);
+    HIPCHK(ctx, hipMemcpy(bcol.data(), f->ell_col_base, sizeof(int) * bcol.size(), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(bval.data(), f->ell_val_base, sizeof(double) * bval.size(), hipMemcpyDeviceToHost));
+    std::vector<std::vector<std::pair<int, double>>> rows((size_t)mp);
+    int w = 1;
+    for (int i = 0; i < mp; ++i) {
+        auto& row = rows[i];
+        for (int e = 0; e < bw; ++e)
+            if (bcol[(size_t)e * mp + i] >= 0) row.emplace_back(bcol[(size_t)e * mp + i], bval[(size_t)e * mp + i]);
+        if (i < d) {
+            const int j = i % N;
+            for (int k = 0; k < C; ++k) {
+                const int col = k * N + j;
+                bool have = false;
+                for (const auto& cv : row) have = have || cv.first == col;
+                if (!have) row.emplace_back(col, 0.0);
+            }
+            std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& x, const std::pair<int, double>& y) {
+                return x.first < y.first;
+            });
+        }
+        w = std::max(w, (int)row.size());
+    }
+    std::vector<int> ecol((size_t)w * mp, -1), slot((size_t)C * mp, 0);
+    std::vector<double> eval((size_t)w * mp, 0.0);
+    for (int i = 0; i < mp; ++i)
+        for (int e = 0; e < (int)rows[i].size(); ++e) {
+            ecol[(size_t)e * mp + i] = rows[i][e].first;
+            eval[(size_t)e * mp + i] = rows[i][e].second;
+            if (i < d && rows[i][e].first % N == i % N) slot[(size_t)(rows[i][e].first / N) * mp + i] = e;
+        }
+    pnmol_reaction_free_ws(f);
+    HIPCHK(ctx, hipMalloc(&f->sys_col, sizeof(int) * ecol.size()));
+    HIPCHK(ctx, hipMalloc(&f->sys_val, sizeof(double) * eval.size()));
+    HIPCHK(ctx, hipMalloc(&f->sys_slot, sizeof(int) * slot.size()));
+    HIPCHK(ctx, hipMemcpy(f->sys_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->sys_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->sys_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
+    f->sys_w = w;
+    f->sys_img_ncomp = C;
+    return 0;
+}
+
 }  // namespace
 
+void pnmol_reaction_free_ws(pnmol_filter* f) {
+    for (void* q : {(void*)f->sys_col, (void*)f->sys_val, (void*)f->sys_slot})
+        if (q) (void)hipFree(q);
+    f->sys_col = nullptr, f->sys_val = nullptr, f->sys_slot = nullptr;
+    f->sys_w = 0, f->sys_img_ncomp = 0;
+}
+
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt) {
-    LinearizeArgs a;
-    a.r = f->reaction;
-    for (int q = 0; q < MAXN; ++q) a.c[q] = 0.0;
+    double c[MAXN];
+    for (int q = 0; q < MAXN; ++q) c[q] = 0.0;
     for (int q = 0; q < f->n; ++q) {
         const double so = frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, q, frame_dt);
-        a.c[q] = f->iwp.A1[q] * (so / nordsieck_scale(f->nu, q, dt));
+        c[q] = f->iwp.A1[q] * (so / nordsieck_scale(f->nu, q, dt));
     }
-    a.s0 = nordsieck_scale(f->nu, 0, dt);
-    k_linearize<<<(unsigned)((f->mp + 255) / 256), 256, 0, f->ctx->stream>>>(a, f->n, mean, f->ell_val, f->ell_val_base,
-                                                                             f->ell_diag_slot, f->shift, f->d, f->dp, f->mp);
+    const unsigned blocks = (unsigned)((f->mp + 255) / 256);
+    if (f->sys_set) {
+        LinearizeSystemArgs a;
+        a.r = f->sys;
+        std::memcpy(a.c, c, sizeof(c));
+        a.s0 = nordsieck_scale(f->nu, 0, dt);
+        k_linearize_system<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, f->d / f->sys.ncomp, mean, f->ell_val, f->sys_val,
+                                                               f->sys_slot, f->shift, f->d, f->dp, f->mp);
+    } else {
+        LinearizeArgs a;
+        a.r = f->reaction;
+        std::memcpy(a.c, c, sizeof(c));
+        a.s0 = nordsieck_scale(f->nu, 0, dt);
+        k_linearize<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot, f->shift,
+                                                        f->d, f->dp, f->mp);
+    }
     HIPCHK(f->ctx, hipGetLastError());
     return 0;
 }
@@ -137,12 +348,68 @@ int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r) {
     if (int rc = restore_base_operator(f)) return rc;
     f->sq_dt = -1.0;  // the error model belongs to the operator that was set
     f->has_reaction = r != nullptr;
+    f->sys_set = false;  // (a filter holds one reaction of either kind)
     if (r) {
         std::memset(&f->reaction, 0, sizeof(f->reaction));
         f->reaction.deg_p = r->deg_p, f->reaction.deg_a = r->deg_a, f->reaction.deg_b = r->deg_b;
         for (int k = 0; k <= r->deg_p; ++k) f->reaction.p[k] = r->p[k];
         for (int k = 0; k <= r->deg_a; ++k) f->reaction.a[k] = r->a[k];
         for (int k = 0; k <= r->deg_b; ++k) f->reaction.b[k] = r->b[k];
+    }
+    return 0;
+}
+
+int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_system* r) {
+    static const char* who = "pnmol_filter_set_reaction_system: ";
+    if (!f) return -1;
+    if (!r) return pnmol_filter_set_reaction(f, nullptr);  // NULL to either setter clears either kind
+    pnmol_ctx* ctx = f->ctx;
+    const char* why = system_descriptor_fault(r);
+    if (!why && f->d % r->ncomp != 0) why = "d is not a multiple of ncomp";
+    if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no pointwise reaction path";
+    if (!why && f->p32) why = "an fp32 filter has no pointwise reaction path";
+    if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
+    if (why) {
+        ctx->err = std::string(who) + why;
+        return -1;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int mp = f->mp;
+    pnmol_drop_graphs(f);  // the descriptor travels by value in the captured launches; width and pointers are baked in too
+    if (f->sys_img_ncomp != r->ncomp || f->sys_w > f->ell_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(st));  // the buffers replaced below may still be read
+        if (f->sys_img_ncomp != r->ncomp)
+            if (int rc = build_system_image(f, r->ncomp)) {
+                pnmol_reaction_free_ws(f);
+                return rc;
+            }
+        if (f->sys_w > f->ell_cap) {
+            if (f->ell_col) (void)hipFree(f->ell_col);
+            if (f->ell_val) (void)hipFree(f->ell_val);
+            f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0, f->ellw = 0, f->ell_is_base = 0;
+            HIPCHK(ctx, hipMalloc(&f->ell_col, sizeof(int) * (size_t)f->sys_w * mp));
+            HIPCHK(ctx, hipMalloc(&f->ell_val, sizeof(double) * (size_t)f->sys_w * mp));
+            f->ell_cap = f->sys_w;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->sys_col, sizeof(int) * (size_t)f->sys_w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->sys_val, sizeof(double) * (size_t)f->sys_w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
+    f->ellw = f->sys_w;
+    f->ell_is_base = 0;  // (restore_base_operator copies the columns back)
+    f->sq_dt = -1.0;     // the error model belongs to the operator that was set
+    f->has_reaction = true;
+    f->sys_set = true;
+    std::memset(&f->sys, 0, sizeof(f->sys));
+    f->sys.ncomp = r->ncomp;
+    for (int c = 0; c < r->ncomp; ++c) {
+        const pnmol_system_poly* src[3] = {&r->p[c], &r->a[c], &r->b[c]};
+        pnmol_system_poly* dst[3] = {&f->sys.p[c], &f->sys.a[c], &f->sys.b[c]};
+        for (int g = 0; g < 3; ++g) {
+            dst[g]->nterms = src[g]->nterms;
+            for (int t = 0; t < src[g]->nterms; ++t) dst[g]->term[t] = src[g]->term[t];
+        }
     }
     return 0;
 }

@@ -75,6 +75,7 @@ SYMBOLS = {
     "pnmol_filter_set_operator": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pnmol_filter_set_operator_diagonal": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pnmol_filter_set_reaction": (ctypes.c_int, [_vp, _vp]),           # (pnmol_reaction*: pde/reactions.py, ReactionDesc)
+    "pnmol_filter_set_reaction_system": (ctypes.c_int, [_vp, _vp]),    # (pnmol_reaction_system*: SystemReactionDesc)
     "pnmol_filter_linearize": (ctypes.c_int, [_vp, _vp, ctypes.c_double]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
@@ -385,11 +386,14 @@ class Filter:
         self.error_model_dt = None
 
     def set_reaction(self, reaction):
-        """A pointwise reaction term (pde/reactions.py) that the device linearises itself, or None to clear it:
-        `pnmol_filter_set_reaction`.  While one is set, `steps` re-linearises in front of every step."""
+        """A pointwise reaction term (pde/reactions.py) that the device linearises itself -- a scalar `Reaction`
+        (`pnmol_filter_set_reaction`) or a coupled `SystemReaction` (`pnmol_filter_set_reaction_system`) --, or None to clear
+        either.  A filter holds one; while one is set, `steps` re-linearises in front of every step."""
+        from .pde.reactions import SystemReaction
+
         desc = None if reaction is None else reaction.to_ctypes()
-        self.ctx.check(self.lib.pnmol_filter_set_reaction(self.handle, None if desc is None else ctypes.byref(desc)),
-                       "pnmol_filter_set_reaction")
+        name = "pnmol_filter_set_reaction_system" if isinstance(reaction, SystemReaction) else "pnmol_filter_set_reaction"
+        self.ctx.check(getattr(self.lib, name)(self.handle, None if desc is None else ctypes.byref(desc)), name)
         self.reaction = reaction
         self.error_model_dt = None
 

@@ -203,6 +203,45 @@ def reaction_diffusion_1d_discretized(reaction, *, bbox=None, t0=0.0, tmax=10.0,
     return pde
 
 
+def reaction_diffusion_system_1d_discretized(reaction, *, diffusion_rates, y0_fun, bbox=None, t0=0.0, tmax=10.0, dx=0.05,
+                                             kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
+                                             stencil_size_boundary=3):
+    """(u_c)_t = D_c (u_c)_xx + r_c(u_0, ..., u_{C-1}) for a coupled pointwise `reaction` (pde/reactions.py, `SystemReaction`),
+    Neumann boundary: the problem class and discretisation of the Lotka-Volterra / SIR recipes above, with f and df taken from
+    the reaction.  `y0_fun(x)` returns the stacked initial values [u_0; ...; u_{C-1}].  `pde.reaction` lets the solver linearise on
+    the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`); the recipes above carry callables only."""
+    diffusion_rates = tuple(float(r) for r in diffusion_rates)
+    if len(diffusion_rates) != reaction.ncomp:
+        raise ValueError(f"expected {reaction.ncomp} diffusion rates, one per species, got {len(diffusion_rates)}")
+    if bbox is None:
+        bbox = [0.0, 1.0]
+    bbox = np.asarray(bbox, dtype=np.float64)
+    f, df, df_diagonal = reaction.callables()
+    laplace = diffops.laplace()
+    pde = problems.SystemSemiLinearEvolutionNeumann(
+        diffop=(laplace,) * reaction.ncomp, diffop_scale=diffusion_rates, bbox=bbox, t0=t0, tmax=tmax, y0_fun=y0_fun, f=f,
+        df=df, df_diagonal=df_diagonal)
+    pde.reaction = reaction
+    mesh_spatial = mesh.RectangularMesh.from_bbox_1d(pde.bbox, step=dx)
+    if kernel is None:
+        kernel = kernels.SquareExponential()
+    pde.discretize_system(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
+                          stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
+    return pde
+
+
+def lotka_volterra_y0(x):
+    """The initial values of `lotka_volterra_1d`."""
+    return np.concatenate((5 * np.ones_like(x), 20.0 * gaussian_bell_1d(x)))
+
+
+def sir_y0(x, bbox=(0.0, 1.0), N=1000.0):
+    """The initial values of `sir_1d`."""
+    init_infectious = 200.0 * gaussian_bell_1d_centered(x, bbox, width=0.5) + 1.0
+    return np.concatenate((N * np.ones_like(init_infectious) - init_infectious, init_infectious,
+                           np.zeros_like(init_infectious)))
+
+
 # Initial-condition defaults; they adhere to Dirichlet conditions (examples.py:344-357)
 
 

@@ -8,6 +8,9 @@ logistic / Fisher-KPP, Allen-Cahn, Nagumo, the spruce-budworm predation term -- 
 
 `Reaction.value` / `Reaction.derivative` are the host form of the same arithmetic (Horner, one rounding per operation,
 r' = P' + (A' B - A B') / B^2), in the kernel's order of operations.
+
+`SystemReaction` (further down) is the coupled form for up to four species on one mesh -- Lotka-Volterra, SIR, Gray-Scott --,
+handed over by `pnmol_filter_set_reaction_system` and linearised by k_linearize_system.
 """
 
 import ctypes
@@ -124,6 +127,214 @@ class Reaction:
         if desc.deg_a < 0 and desc.deg_b < 0:
             return cls(p=p)
         return cls(p=p, a=tuple(desc.a[: desc.deg_a + 1]), b=tuple(desc.b[: desc.deg_b + 1]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Coupled systems: C species on the same mesh, state [u_0; ...; u_{C-1}], r_c(u) = P_c(u) + A_c(u) / B_c(u) with u the C values at
+# ONE mesh point (`pnmol_filter_set_reaction_system`, k_linearize_system).  The Jacobian is block-dense with diagonal blocks.
+
+MAXCOMP = 4    # PNMOL_SYSTEM_MAXCOMP
+MAXTERMS = 8   # PNMOL_SYSTEM_MAXTERMS
+MAXPOW = 7
+
+
+class MonomialDesc(ctypes.Structure):
+    """`pnmol_monomial`."""
+
+    _fields_ = [("coef", ctypes.c_double), ("pow", ctypes.c_int * MAXCOMP)]
+
+
+class SystemPolyDesc(ctypes.Structure):
+    """`pnmol_system_poly`."""
+
+    _fields_ = [("nterms", ctypes.c_int), ("term", MonomialDesc * MAXTERMS)]
+
+
+class SystemReactionDesc(ctypes.Structure):
+    """`pnmol_reaction_system` of include/pnmol_hip.h."""
+
+    _fields_ = [("ncomp", ctypes.c_int), ("p", SystemPolyDesc * MAXCOMP), ("a", SystemPolyDesc * MAXCOMP),
+                ("b", SystemPolyDesc * MAXCOMP)]
+
+
+def _system_poly(name, terms, ncomp):
+    """Validated tuple of (coef, exponents) terms; exponents are padded to MAXCOMP."""
+    terms = () if terms is None else tuple(terms)
+    if len(terms) > MAXTERMS:
+        raise ValueError(f"SystemReaction: {name} has {len(terms)} terms, the largest supported number is {MAXTERMS}")
+    out = []
+    for term in terms:
+        try:
+            coef, pw = term
+            coef, pw = float(coef), tuple(int(e) for e in pw)
+            exact = all(e == f for e, f in zip(pw, term[1]))
+        except (TypeError, ValueError):
+            raise ValueError(f"SystemReaction: a term of {name} is not (coefficient, exponents): {term!r}") from None
+        if not exact or len(pw) > MAXCOMP:
+            raise ValueError(f"SystemReaction: a term of {name} is not (coefficient, exponents): {term!r}")
+        pw = pw + (0,) * (MAXCOMP - len(pw))
+        if any(e < 0 or e > MAXPOW for e in pw):
+            raise ValueError(f"SystemReaction: {name} has an exponent outside [0, {MAXPOW}]")
+        if any(pw[ncomp:]):
+            raise ValueError(f"SystemReaction: {name} has a non-zero exponent of a species >= ncomp = {ncomp}")
+        if not np.isfinite(coef):
+            raise ValueError(f"SystemReaction: {name} has a coefficient that is not finite")
+        out.append((coef, pw))
+    return tuple(out)
+
+
+def _monomial(start, pw, less, u):
+    """start * u_0^pw[0] * u_1^pw[1] * ..., one multiplication at a time; `less` takes one factor off that species."""
+    m = np.full_like(u[0], start)
+    for k in range(len(u)):
+        for _ in range(pw[k] - (1 if k == less else 0)):
+            m = m * u[k]
+    return m
+
+
+def _system_poly_eval(terms, u):
+    """(value, [partial derivative by u_k for every k]) of a polynomial at the species values u (a list of arrays): the sum
+    of the terms in the order given, starting from the first one."""
+    v, dv = None, [None] * len(u)
+    for coef, pw in terms:
+        m = _monomial(coef, pw, -1, u)
+        v = m if v is None else v + m
+        for k in range(len(u)):
+            if pw[k] >= 1:
+                dm = _monomial(pw[k] * coef, pw, k, u)
+                dv[k] = dm if dv[k] is None else dv[k] + dm
+    zero = np.zeros_like(u[0])
+    return (zero if v is None else v), [zero if x is None else x for x in dv]
+
+
+class SystemReaction:
+    """r_c(u) = P_c(u) + A_c(u) / B_c(u) for c < ncomp <= 4: `p`, `a`, `b` are per-component sequences of polynomials, each a
+    sequence of at most 8 terms (coef, exponents) meaning coef * u_0^e_0 * u_1^e_1 ... (exponents 0..7, scalars the same at every
+    mesh point; an empty sequence is the zero polynomial).  `a[c]` and `b[c]` come together or not at all (empty or None)."""
+
+    def __init__(self, ncomp, p, a=None, b=None):
+        ncomp = int(ncomp)
+        if not 1 <= ncomp <= MAXCOMP:
+            raise ValueError(f"SystemReaction: ncomp = {ncomp} is outside [1, {MAXCOMP}]")
+        self.ncomp = ncomp
+        if (a is None) != (b is None):
+            raise ValueError("SystemReaction: the numerators a and the denominators b are given together or not at all")
+        groups = {"p": p, "a": a if a is not None else [()] * ncomp, "b": b if b is not None else [()] * ncomp}
+        for name, polys in groups.items():
+            if len(polys) != ncomp:
+                raise ValueError(f"SystemReaction: {name} has {len(polys)} entries for ncomp = {ncomp} components")
+            setattr(self, name, tuple(_system_poly(f"{name}[{c}]", polys[c], ncomp) for c in range(ncomp)))
+        for c in range(ncomp):
+            if bool(self.a[c]) != bool(self.b[c]):
+                raise ValueError(f"SystemReaction: the numerator a[{c}] and the denominator b[{c}] are given together or not "
+                                 f"at all")
+            if self.b[c] and not any(coef for coef, _ in self.b[c]):
+                raise ValueError(f"SystemReaction: the denominator b[{c}] is identically zero")
+
+    def __repr__(self):
+        return f"SystemReaction(ncomp={self.ncomp}, p={self.p!r}, a={self.a!r}, b={self.b!r})"
+
+    # ------------------------------------------------------------------ host arithmetic (the kernel's, in its order)
+    def _species(self, u):
+        u = np.asarray(u, dtype=np.float64)
+        if u.ndim != 1 or u.shape[0] % self.ncomp:
+            raise ValueError(f"SystemReaction: expected a vector of ncomp * N = {self.ncomp} * N entries, got shape {u.shape}")
+        return list(u.reshape(self.ncomp, -1))
+
+    def _value_and_jacobian(self, u):
+        u = self._species(u)
+        C = self.ncomp
+        r, J = [], []
+        for c in range(C):
+            P, dP = _system_poly_eval(self.p[c], u)
+            if self.a[c]:
+                A, dA = _system_poly_eval(self.a[c], u)
+                B, dB = _system_poly_eval(self.b[c], u)
+                r.append(P + A / B)
+                J.append([dP[k] + (dA[k] * B - A * dB[k]) / (B * B) for k in range(C)])
+            else:
+                r.append(P)
+                J.append(dP)
+        return u, np.array(r), np.array(J)
+
+    def value(self, u):
+        """r at the state u = [u_0; ...; u_{C-1}] (C N entries): C N entries."""
+        return self._value_and_jacobian(u)[1].reshape(-1)
+
+    def jacobian_blocks(self, u):
+        """(C, C, N): entry [c, k, j] = d r_c / d u_k at mesh point j."""
+        return self._value_and_jacobian(u)[2]
+
+    def shift(self, u):
+        """((J_c0 u_0 + J_c1 u_1) + ...) - r_c: the shift of the EK1 linearisation at u (C N entries)."""
+        us, r, J = self._value_and_jacobian(u)
+        out = []
+        for c in range(self.ncomp):
+            acc = J[c, 0] * us[0]
+            for k in range(1, self.ncomp):
+                acc = acc + J[c, k] * us[k]
+            out.append(acc - r[c])
+        return np.array(out).reshape(-1)
+
+    def jacobian(self, u):
+        """The dense (C N, C N) Jacobian: a block matrix of diagonals."""
+        J = self.jacobian_blocks(u)
+        C, N = self.ncomp, J.shape[2]
+        out = np.zeros((C * N, C * N))
+        idx = np.arange(N)
+        for c in range(C):
+            for k in range(C):
+                out[c * N + idx, k * N + idx] = J[c, k]
+        return out
+
+    def callables(self):
+        """(f(t, u), df(t, u) as a dense block matrix of diagonals, None): what the system problem classes take."""
+        def f(_t, u):
+            return self.value(u)
+
+        def df(_t, u):
+            return self.jacobian(u)
+
+        return f, df, None
+
+    # ------------------------------------------------------------------ C ABI
+    def to_ctypes(self):
+        desc = SystemReactionDesc()
+        desc.ncomp = self.ncomp
+        for dst, src in ((desc.p, self.p), (desc.a, self.a), (desc.b, self.b)):
+            for c in range(self.ncomp):
+                dst[c].nterms = len(src[c])
+                for t, (coef, pw) in enumerate(src[c]):
+                    dst[c].term[t].coef = coef
+                    for k in range(MAXCOMP):
+                        dst[c].term[t].pow[k] = pw[k]
+        return desc
+
+    @classmethod
+    def from_ctypes(cls, desc):
+        C = desc.ncomp
+
+        def polys(group):
+            return [[(group[c].term[t].coef, tuple(group[c].term[t].pow)) for t in range(group[c].nterms)] for c in range(C)]
+
+        return cls(C, polys(desc.p), polys(desc.a), polys(desc.b))
+
+
+def lotka_volterra(a=0.5, b=0.05, c=0.05, d=0.5):
+    """Predator-prey: (a u - b u v, c u v - d v)."""
+    return SystemReaction(2, p=[[(a, (1, 0)), (-b, (1, 1))], [(c, (1, 1)), (-d, (0, 1))]])
+
+
+def sir(beta=0.3, gamma=0.07):
+    """(-beta s i / (s + i + r), beta s i / (s + i + r) - gamma i, gamma i): no pole while the population is positive."""
+    total = [(1.0, (1, 0, 0)), (1.0, (0, 1, 0)), (1.0, (0, 0, 1))]
+    return SystemReaction(3, p=[[], [(-gamma, (0, 1, 0))], [(gamma, (0, 1, 0))]],
+                          a=[[(-beta, (1, 1, 0))], [(beta, (1, 1, 0))], []], b=[total, total, []])
+
+
+def gray_scott(feed, kill):
+    """(-u v^2 + feed (1 - u), u v^2 - (feed + kill) v)."""
+    return SystemReaction(2, p=[[(-1.0, (1, 2)), (feed, (0, 0)), (-feed, (1, 0))], [(1.0, (1, 2)), (-(feed + kill), (0, 1))]])
 
 
 def logistic(rate=1.0):

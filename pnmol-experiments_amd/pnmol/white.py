@@ -506,7 +506,8 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return None
         return np.asarray(dfd(t, m_at), dtype=np.float64)
 
-    # A problem with a `reaction` attribute (pde/reactions.py; `pde.examples.reaction_diffusion_1d_discretized`) is linearised on
+    # A problem with a `reaction` attribute (pde/reactions.py, a scalar `Reaction` or a coupled `SystemReaction`;
+    # `pde.examples.reaction_diffusion_1d_discretized`, `reaction_diffusion_system_1d_discretized`) is linearised on
     # the device: `attempt_step` takes no host round trip and `solve_marginals` runs.  False: the host callables, as for
     # every other semilinear problem.  fp64 covariance-form white-noise solvers only; the others use the callables.
     reaction_on_device = True
