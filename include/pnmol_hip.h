@@ -196,6 +196,29 @@ typedef struct pnmol_reaction_system {
 } pnmol_reaction_system;                           /* r_c(u) = P_c(u) + A_c(u) / B_c(u), u = (u_0..u_{C-1}) at ONE mesh point */
 int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_system* r);   /* NULL clears */
 
+/* Convection terms (Burgers type) --------------------------------------------------------------------------------------------
+ * For u_t = L u + c(u) . (G u) + r(u): c a polynomial in ascending coefficients (degree <= 7; viscous Burgers: c = (0, -1)), r an
+ * optional `pnmol_reaction` (all three degrees -1: absent; Burgers-Fisher: the logistic term), G a (d, d) stencil matrix (row
+ * major; a discretised gradient on the mesh) that is fixed when the term is set.  With u the predicted mean, g = G u and
+ * q_i = c'(u_i) g_i + r'(u_i), the EK1 linearisation is M = L + diag(c(u)) G + diag(q) with shift_i = q_i u_i - r(u_i): the
+ * Jacobian touches every stencil entry of a row, not only its diagonal.
+ * `pnmol_filter_set_convection` (a NULL term clears, G is then ignored) mirrors `pnmol_filter_set_reaction`: it stores the
+ * descriptor, builds and installs the union image of the L given at creation and of G -- every PDE row has a slot for each column
+ * in which L or G has an entry, in ascending column order, with G's value beside it (0 where only L has one); the stencil grows if
+ * the union is wider than L -- with a zero shift, forgets the error model and drops captured graphs.  A filter holds one of
+ * reaction, system or convection: each setter replaces what another had set, NULL to any of them clears, and the cleared filter
+ * behaves bit for bit like one that never had a term.  While a convection term is set the operator calls are refused and
+ * `pnmol_filter_linearize` and `pnmol_filter_steps(_begin)` re-linearise, as for a reaction.
+ * Arithmetic (every operation rounded on its own; pnmol/pde/reactions.py, `Convection`, is the same on the host): u_i and the u of
+ * every slot column as in `pnmol_filter_predict_mean`; g_i is the sum of G_ij u_j over the row's entries of G that are not zero,
+ * in ascending column order, starting from the first product; c, c', r, r' by Horner as for a reaction; q = c' g + r' (c' g alone
+ * without a reaction); an entry of M is L_ij + c_i G_ij, the diagonal one (L_ii + c_i G_ii) + q_i; the shift is q u - r.
+ * -1 (reason in `pnmol_last_error`): null filter, a term without G, a degree outside [-1, 7], A without B or B without A, a
+ * coefficient or an entry of G that is not finite, B identically zero, latent-force filter, fp32 filter, a row of L without a
+ * diagonal entry.  The uncertainty of the finite-difference weights of G is not modelled (the error model keeps that of L). */
+typedef struct pnmol_convection { int deg_c; double c[PNMOL_REACTION_MAXDEG + 1]; pnmol_reaction r; } pnmol_convection;
+int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, const double* G_dd);   /* NULL term clears */
+
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);
 int pnmol_state_destroy(pnmol_state* s); /* -1 for the target of an unfinished pnmol_filter_steps_begin */

@@ -183,6 +183,16 @@ struct pnmol_filter {
     double* sys_val = nullptr;
     int* sys_slot = nullptr;
     int sys_w = 0, sys_img_ncomp = 0;
+    // ... or a convection term c(u) . (G u) + r(u) (pnmol_filter_set_convection), has_reaction with cv_set: the union image of the
+    // creation-time operator and G (cv_w wide; columns, -L's values, G's value per slot, 0 where only L has an entry) and the
+    // slot of every PDE row's diagonal entry in it.  Rebuilt by every set call (G comes with the term).
+    bool cv_set = false;
+    pnmol_convection cv{};
+    int* cv_col = nullptr;
+    double* cv_val = nullptr;
+    double* cv_g = nullptr;
+    int* cv_slot = nullptr;
+    int cv_w = 0;
 };
 
 struct pnmol_state {
@@ -260,10 +270,10 @@ void pnmol_observe_free_ws(pnmol_filter* f);
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
 
 void pnmol_reaction_free_ws(pnmol_filter* f);
-// pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system) on the ctx stream for one step over dt from
-// the mean `mean` (Dp, in the frame frame_dt; 0 = raw coordinates): the diagonal (same-point) slots of ell_val and the shift
-// become those of the EK1 linearisation of the reaction at the predicted mean.  Needs f->has_reaction; no synchronisation.
-// -2: the launch failed.
+// pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system, k_linearize_convection for a convection
+// term) on the ctx stream for one step over dt from the mean `mean` (Dp, in the frame frame_dt; 0 = raw coordinates): the
+// diagonal (same-point; for a convection term all) slots of ell_val and the shift become those of the EK1 linearisation of the
+// term at the predicted mean.  Needs f->has_reaction; no synchronisation.  -2: the launch failed.
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);

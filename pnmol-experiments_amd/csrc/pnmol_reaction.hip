@@ -11,6 +11,11 @@
 // Coupled systems of C <= 4 species (`pnmol_filter_set_reaction_system`; Lotka-Volterra, SIR): r_c depends on all species at the
 // same mesh point, so row c N + j of the Jacobian has C entries, at the columns k N + j.  The setter widens the stencil image
 // of L by those columns once (build_system_image), and k_linearize_system patches the C same-point slots of every row.
+//
+// Convection terms (`pnmol_filter_set_convection`; viscous Burgers, Burgers-Fisher): f(u)_i = c(u_i) (G u)_i + r(u_i) with a
+// stencil operator G.  The Jacobian diag(c) G + diag(c' G u + r') touches every entry of a stencil row, so the setter builds the
+// union image of L and G with G's value beside every slot (build_convection_image) and k_linearize_convection rewrites all slots
+// of a row; the shift (c' g + r') u - r needs no product with G (the c g terms of J u - f cancel).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -179,6 +184,74 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a,
     shift[i] = Ju - r;
 }
 
+// ---- convection terms: f(u)_i = c(u_i) (G u)_i + r(u_i) (pnmol_filter_set_convection)
+struct LinearizeConvectionArgs {
+    pnmol_convection t;
+    double c[MAXN];  // as in LinearizeArgs
+    double s0;
+};
+
+// derivative 0 of the predicted mean at mesh point j, in raw coordinates: k_linearize's arithmetic
+__device__ __forceinline__ double predicted_value(const double (&c)[MAXN], double s0, int n, const double* __restrict__ mean,
+                                                  int dp, int j) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int q = 0; q < n; ++q) acc = acc + c[q] * mean[(long)q * dp + j];
+    return s0 * acc;
+}
+
+// One thread per measurement row i: u_i and the u of the row's slot columns (recomputed per slot: one launch, no grid-wide
+// dependency), g_i = (G u)_i over the entries of G that are not zero in slot (= ascending column) order starting from the first
+// product, c, c', r, r' by Horner, q = c' g + r'; every slot becomes base - c G, the diagonal one loses q as well, and the shift
+// is q u - r.  Every operation is rounded on its own, in the order of Convection.linearization (pnmol/pde/reactions.py).
+// img_col / img_val / img_g: the union image of the creation-time operator and G (w slots, packed to the front of every row).
+__global__ __launch_bounds__(256) void k_linearize_convection(LinearizeConvectionArgs a, int n, int w,
+                                                              const double* __restrict__ mean, double* __restrict__ ell_val,
+                                                              const int* __restrict__ img_col, const double* __restrict__ img_val,
+                                                              const double* __restrict__ img_g, const int* __restrict__ slot,
+                                                              double* __restrict__ shift, int d, int dp, int mp) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= mp) return;
+    if (i >= d) {
+        shift[i] = 0.0;
+        return;
+    }
+    const double u = predicted_value(a.c, a.s0, n, mean, dp, i);
+    double g = 0.0;
+    bool first = true;
+    for (int e = 0; e < w; ++e) {
+        const int col = img_col[(long)e * mp + i];
+        if (col < 0) break;
+        const double gv = img_g[(long)e * mp + i];
+        if (gv == 0.0) continue;
+        const double prod = gv * predicted_value(a.c, a.s0, n, mean, dp, col);
+        g = first ? prod : g + prod;
+        first = false;
+    }
+    double cu, dcu, P, dP, A, dA, B, dB;
+    horner(a.t.c, a.t.deg_c, u, cu, dcu);
+    horner(a.t.r.p, a.t.r.deg_p, u, P, dP);
+    double r = P, dr = dP;
+    if (a.t.r.deg_a >= 0) {
+        horner(a.t.r.a, a.t.r.deg_a, u, A, dA);
+        horner(a.t.r.b, a.t.r.deg_b, u, B, dB);
+        r = P + A / B;
+        dr = dP + (dA * B - A * dB) / (B * B);
+    }
+    double q = dcu * g;
+    if (a.t.r.deg_p >= 0 || a.t.r.deg_a >= 0) q = q + dr;
+    const int ds = slot[i];
+    for (int e = 0; e < w; ++e) {
+        const long at = (long)e * mp + i;
+        if (img_col[at] < 0) break;
+        double v = img_val[at] - cu * img_g[at];
+        if (e == ds) v = v - q;
+        ell_val[at] = v;
+    }
+    shift[i] = q * u - r;
+}
+
 // the stencil rows of the operator given at creation and a zero shift (what pnmol_filter_set_operator_diagonal restores
 // after a dense upload), on the ctx stream
 int restore_base_operator(pnmol_filter* f) {
@@ -198,6 +271,22 @@ bool all_finite(const double* c, int deg) {
     for (int k = 0; k <= deg; ++k)
         if (!std::isfinite(c[k])) return false;
     return true;
+}
+
+// why a reaction descriptor is refused, or nullptr
+const char* reaction_descriptor_fault(const pnmol_reaction* r) {
+    const int degs[3] = {r->deg_p, r->deg_a, r->deg_b};
+    for (int g : degs)
+        if (g < -1 || g > PNMOL_REACTION_MAXDEG) return "a degree outside [-1, 7]";
+    if ((r->deg_a < 0) != (r->deg_b < 0)) return "the numerator a and the denominator b are given together or not at all";
+    if (!(all_finite(r->p, r->deg_p) && all_finite(r->a, r->deg_a) && all_finite(r->b, r->deg_b)))
+        return "a coefficient is not finite";
+    if (r->deg_b >= 0) {
+        bool zero = true;
+        for (int k = 0; k <= r->deg_b; ++k) zero = zero && r->b[k] == 0.0;
+        if (zero) return "the denominator b is identically zero";
+    }
+    return nullptr;
 }
 
 // why a system descriptor is refused, or nullptr
@@ -225,6 +314,13 @@ const char* system_descriptor_fault(const pnmol_reaction_system* r) {
         }
     }
     return nullptr;
+}
+
+void free_system_image(pnmol_filter* f) {
+    for (void* q : {(void*)f->sys_col, (void*)f->sys_val, (void*)f->sys_slot})
+        if (q) (void)hipFree(q);
+    f->sys_col = nullptr, f->sys_val = nullptr, f->sys_slot = nullptr;
+    f->sys_w = 0, f->sys_img_ncomp = 0;
 }
 
 // The widened image of the operator given at creation for C species: every PDE row i = c N + j has a slot for each column
@@ -265,7 +361,7 @@ int build_system_image(pnmol_filter* f, int C) {
             eval[(size_t)e * mp + i] = rows[i][e].second;
             if (i < d && rows[i][e].first % N == i % N) slot[(size_t)(rows[i][e].first / N) * mp + i] = e;
         }
-    pnmol_reaction_free_ws(f);
+    free_system_image(f);
     HIPCHK(ctx, hipMalloc(&f->sys_col, sizeof(int) * ecol.size()));
     HIPCHK(ctx, hipMalloc(&f->sys_val, sizeof(double) * eval.size()));
     HIPCHK(ctx, hipMalloc(&f->sys_slot, sizeof(int) * slot.size()));
@@ -277,13 +373,71 @@ int build_system_image(pnmol_filter* f, int C) {
     return 0;
 }
 
+void free_convection_image(pnmol_filter* f) {
+    for (void* q : {(void*)f->cv_col, (void*)f->cv_val, (void*)f->cv_g, (void*)f->cv_slot})
+        if (q) (void)hipFree(q);
+    f->cv_col = nullptr, f->cv_val = nullptr, f->cv_g = nullptr, f->cv_slot = nullptr;
+    f->cv_w = 0;
+}
+
+// The union image of the operator given at creation and G (d x d, row major): every PDE row has a slot for each column in which
+// either has an entry (the value of -L there, or 0), slots in ascending column order as build_ell leaves them, and G's value
+// beside each slot; boundary rows as they are.  Built on the host from the base image and kept on the device beside the table
+// of the diagonal slots.  The caller has synchronised the stream: the buffers replaced here may have been read.
+int build_convection_image(pnmol_filter* f, const double* G) {
+    pnmol_ctx* ctx = f->ctx;
+    const int d = f->d, mp = f->mp, bw = f->base_w;
+    std::vector<int> bcol((size_t)bw * mp);
+    std::vector<double> bval((size_t)bw * mp);
+    HIPCHK(ctx, hipMemcpy(bcol.data(), f->ell_col_base, sizeof(int) * bcol.size(), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(bval.data(), f->ell_val_base, sizeof(double) * bval.size(), hipMemcpyDeviceToHost));
+    std::vector<std::vector<std::pair<int, double>>> rows((size_t)mp);
+    int w = 1;
+    for (int i = 0; i < mp; ++i) {
+        auto& row = rows[i];
+        for (int e = 0; e < bw; ++e)
+            if (bcol[(size_t)e * mp + i] >= 0) row.emplace_back(bcol[(size_t)e * mp + i], bval[(size_t)e * mp + i]);
+        if (i < d) {
+            for (int k = 0; k < d; ++k) {
+                if (G[(size_t)i * d + k] == 0.0) continue;
+                bool have = false;
+                for (const auto& cv : row) have = have || cv.first == k;
+                if (!have) row.emplace_back(k, 0.0);
+            }
+            std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& x, const std::pair<int, double>& y) {
+                return x.first < y.first;
+            });
+        }
+        w = std::max(w, (int)row.size());
+    }
+    std::vector<int> ecol((size_t)w * mp, -1), slot((size_t)mp, 0);
+    std::vector<double> eval((size_t)w * mp, 0.0), eg((size_t)w * mp, 0.0);
+    for (int i = 0; i < mp; ++i)
+        for (int e = 0; e < (int)rows[i].size(); ++e) {
+            const int col = rows[i][e].first;
+            ecol[(size_t)e * mp + i] = col;
+            eval[(size_t)e * mp + i] = rows[i][e].second;
+            if (i < d && col < d) eg[(size_t)e * mp + i] = G[(size_t)i * d + col];
+            if (i < d && col == i) slot[i] = e;
+        }
+    free_convection_image(f);
+    HIPCHK(ctx, hipMalloc(&f->cv_col, sizeof(int) * ecol.size()));
+    HIPCHK(ctx, hipMalloc(&f->cv_val, sizeof(double) * eval.size()));
+    HIPCHK(ctx, hipMalloc(&f->cv_g, sizeof(double) * eg.size()));
+    HIPCHK(ctx, hipMalloc(&f->cv_slot, sizeof(int) * slot.size()));
+    HIPCHK(ctx, hipMemcpy(f->cv_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->cv_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->cv_g, eg.data(), sizeof(double) * eg.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->cv_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
+    f->cv_w = w;
+    return 0;
+}
+
 }  // namespace
 
 void pnmol_reaction_free_ws(pnmol_filter* f) {
-    for (void* q : {(void*)f->sys_col, (void*)f->sys_val, (void*)f->sys_slot})
-        if (q) (void)hipFree(q);
-    f->sys_col = nullptr, f->sys_val = nullptr, f->sys_slot = nullptr;
-    f->sys_w = 0, f->sys_img_ncomp = 0;
+    free_system_image(f);
+    free_convection_image(f);
 }
 
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt) {
@@ -294,7 +448,14 @@ int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt,
         c[q] = f->iwp.A1[q] * (so / nordsieck_scale(f->nu, q, dt));
     }
     const unsigned blocks = (unsigned)((f->mp + 255) / 256);
-    if (f->sys_set) {
+    if (f->cv_set) {
+        LinearizeConvectionArgs a;
+        a.t = f->cv;
+        std::memcpy(a.c, c, sizeof(c));
+        a.s0 = nordsieck_scale(f->nu, 0, dt);
+        k_linearize_convection<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, f->cv_w, mean, f->ell_val, f->cv_col, f->cv_val,
+                                                                   f->cv_g, f->cv_slot, f->shift, f->d, f->dp, f->mp);
+    } else if (f->sys_set) {
         LinearizeSystemArgs a;
         a.r = f->sys;
         std::memcpy(a.c, c, sizeof(c));
@@ -320,18 +481,7 @@ int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r) {
     if (!f) return -1;
     pnmol_ctx* ctx = f->ctx;
     if (r) {
-        const char* why = nullptr;
-        const int degs[3] = {r->deg_p, r->deg_a, r->deg_b};
-        for (int g : degs)
-            if (g < -1 || g > PNMOL_REACTION_MAXDEG) why = "a degree outside [-1, 7]";
-        if (!why && (r->deg_a < 0) != (r->deg_b < 0)) why = "the numerator a and the denominator b are given together or not at all";
-        if (!why && !(all_finite(r->p, r->deg_p) && all_finite(r->a, r->deg_a) && all_finite(r->b, r->deg_b)))
-            why = "a coefficient is not finite";
-        if (!why && r->deg_b >= 0) {
-            bool zero = true;
-            for (int k = 0; k <= r->deg_b; ++k) zero = zero && r->b[k] == 0.0;
-            if (zero) why = "the denominator b is identically zero";
-        }
+        const char* why = reaction_descriptor_fault(r);
         if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no pointwise reaction path";
         if (!why && f->p32) why = "an fp32 filter has no pointwise reaction path";
         if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
@@ -348,7 +498,8 @@ int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r) {
     if (int rc = restore_base_operator(f)) return rc;
     f->sq_dt = -1.0;  // the error model belongs to the operator that was set
     f->has_reaction = r != nullptr;
-    f->sys_set = false;  // (a filter holds one reaction of either kind)
+    f->sys_set = false;  // (a filter holds one term of any kind)
+    f->cv_set = false;
     if (r) {
         std::memset(&f->reaction, 0, sizeof(f->reaction));
         f->reaction.deg_p = r->deg_p, f->reaction.deg_a = r->deg_a, f->reaction.deg_b = r->deg_b;
@@ -381,7 +532,7 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
         HIPCHK(ctx, hipStreamSynchronize(st));  // the buffers replaced below may still be read
         if (f->sys_img_ncomp != r->ncomp)
             if (int rc = build_system_image(f, r->ncomp)) {
-                pnmol_reaction_free_ws(f);
+                free_system_image(f);
                 return rc;
             }
         if (f->sys_w > f->ell_cap) {
@@ -401,6 +552,7 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
     f->sq_dt = -1.0;     // the error model belongs to the operator that was set
     f->has_reaction = true;
     f->sys_set = true;
+    f->cv_set = false;
     std::memset(&f->sys, 0, sizeof(f->sys));
     f->sys.ncomp = r->ncomp;
     for (int c = 0; c < r->ncomp; ++c) {
@@ -411,6 +563,67 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
             for (int t = 0; t < src[g]->nterms; ++t) dst[g]->term[t] = src[g]->term[t];
         }
     }
+    return 0;
+}
+
+int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, const double* G_dd) {
+    static const char* who = "pnmol_filter_set_convection: ";
+    if (!f) return -1;
+    if (!term) return pnmol_filter_set_reaction(f, nullptr);  // NULL to any setter clears any kind
+    pnmol_ctx* ctx = f->ctx;
+    const char* why = nullptr;
+    if (!G_dd) why = "a convection term needs its operator G";
+    if (!why && (term->deg_c < -1 || term->deg_c > PNMOL_REACTION_MAXDEG)) why = "a degree outside [-1, 7]";
+    if (!why) why = reaction_descriptor_fault(&term->r);
+    if (!why && !all_finite(term->c, term->deg_c)) why = "a coefficient is not finite";
+    if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no convection path";
+    if (!why && f->p32) why = "an fp32 filter has no convection path";
+    if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
+    if (!why)
+        for (size_t k = 0; k < (size_t)f->d * f->d && !why; ++k)
+            if (!std::isfinite(G_dd[k])) why = "an entry of G is not finite";
+    if (why) {
+        ctx->err = std::string(who) + why;
+        return -1;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int mp = f->mp;
+    pnmol_drop_graphs(f);  // the descriptor travels by value in the captured launches; width and pointers are baked in too
+    HIPCHK(ctx, hipStreamSynchronize(st));  // the image replaced below may still be read
+    f->cv_set = false;
+    if (int rc = build_convection_image(f, G_dd)) {
+        // no image: leave the filter without a term, on the operator given at creation
+        free_convection_image(f);
+        f->has_reaction = false, f->sys_set = false;
+        (void)restore_base_operator(f);
+        f->sq_dt = -1.0;
+        return rc;
+    }
+    if (f->cv_w > f->ell_cap) {
+        if (f->ell_col) (void)hipFree(f->ell_col);
+        if (f->ell_val) (void)hipFree(f->ell_val);
+        f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0, f->ellw = 0, f->ell_is_base = 0;
+        HIPCHK(ctx, hipMalloc(&f->ell_col, sizeof(int) * (size_t)f->cv_w * mp));
+        HIPCHK(ctx, hipMalloc(&f->ell_val, sizeof(double) * (size_t)f->cv_w * mp));
+        f->ell_cap = f->cv_w;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->cv_col, sizeof(int) * (size_t)f->cv_w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->cv_val, sizeof(double) * (size_t)f->cv_w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
+    f->ellw = f->cv_w;
+    f->ell_is_base = 0;  // (restore_base_operator copies the columns back)
+    f->sq_dt = -1.0;     // the error model belongs to the operator that was set
+    f->has_reaction = true;
+    f->sys_set = false;
+    f->cv_set = true;
+    std::memset(&f->cv, 0, sizeof(f->cv));
+    f->cv.deg_c = term->deg_c;
+    for (int k = 0; k <= term->deg_c; ++k) f->cv.c[k] = term->c[k];
+    f->cv.r.deg_p = term->r.deg_p, f->cv.r.deg_a = term->r.deg_a, f->cv.r.deg_b = term->r.deg_b;
+    for (int k = 0; k <= term->r.deg_p; ++k) f->cv.r.p[k] = term->r.p[k];
+    for (int k = 0; k <= term->r.deg_a; ++k) f->cv.r.a[k] = term->r.a[k];
+    for (int k = 0; k <= term->r.deg_b; ++k) f->cv.r.b[k] = term->r.b[k];
     return 0;
 }
 

@@ -76,6 +76,7 @@ SYMBOLS = {
     "pnmol_filter_set_operator_diagonal": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pnmol_filter_set_reaction": (ctypes.c_int, [_vp, _vp]),           # (pnmol_reaction*: pde/reactions.py, ReactionDesc)
     "pnmol_filter_set_reaction_system": (ctypes.c_int, [_vp, _vp]),    # (pnmol_reaction_system*: SystemReactionDesc)
+    "pnmol_filter_set_convection": (ctypes.c_int, [_vp, _vp, _c_double_p]),   # (pnmol_convection*: ConvectionDesc; G (d, d))
     "pnmol_filter_linearize": (ctypes.c_int, [_vp, _vp, ctypes.c_double]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
@@ -387,13 +388,22 @@ class Filter:
 
     def set_reaction(self, reaction):
         """A pointwise reaction term (pde/reactions.py) that the device linearises itself -- a scalar `Reaction`
-        (`pnmol_filter_set_reaction`) or a coupled `SystemReaction` (`pnmol_filter_set_reaction_system`) --, or None to clear
-        either.  A filter holds one; while one is set, `steps` re-linearises in front of every step."""
-        from .pde.reactions import SystemReaction
+        (`pnmol_filter_set_reaction`), a coupled `SystemReaction` (`pnmol_filter_set_reaction_system`) or a `Convection` term
+        with its operator G (`pnmol_filter_set_convection`) --, or None to clear any of them.  A filter holds one; while one is
+        set, `steps` re-linearises in front of every step."""
+        from .pde.reactions import Convection, SystemReaction
 
         desc = None if reaction is None else reaction.to_ctypes()
-        name = "pnmol_filter_set_reaction_system" if isinstance(reaction, SystemReaction) else "pnmol_filter_set_reaction"
-        self.ctx.check(getattr(self.lib, name)(self.handle, None if desc is None else ctypes.byref(desc)), name)
+        if isinstance(reaction, Convection):
+            if reaction.G is None:
+                raise ValueError("the convection term has no operator G (Convection.set_operator; the problem recipes set it)")
+            name = "pnmol_filter_set_convection"
+            G = _f64(reaction.G, (self.d, self.d))
+            rc = self.lib.pnmol_filter_set_convection(self.handle, ctypes.byref(desc), _dp(G))
+        else:
+            name = "pnmol_filter_set_reaction_system" if isinstance(reaction, SystemReaction) else "pnmol_filter_set_reaction"
+            rc = getattr(self.lib, name)(self.handle, None if desc is None else ctypes.byref(desc))
+        self.ctx.check(rc, name)
         self.reaction = reaction
         self.error_model_dt = None
 

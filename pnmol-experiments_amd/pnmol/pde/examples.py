@@ -9,8 +9,8 @@ import functools
 
 import numpy as np
 
-from .. import diffops, kernels, mesh
-from . import problems
+from .. import diffops, discretize, kernels, mesh
+from . import problems, reactions
 
 
 def heat_1d_discretized(*, bbox=None, dx=0.05, stencil_size_interior=3, stencil_size_boundary=3, t0=0.0, tmax=5.0,
@@ -201,6 +201,43 @@ def reaction_diffusion_1d_discretized(reaction, *, bbox=None, t0=0.0, tmax=10.0,
     pde.discretize(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
                    stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
     return pde
+
+
+def convection_diffusion_1d_discretized(term, *, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=1.0, y0_fun=None, dx=0.1,
+                                        kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
+                                        stencil_size_boundary=3, gradient_stencil_size=3, bcond="dirichlet"):
+    """u_t = kappa u_xx + c(u) u_x + r(u) for a convection `term` (pde/reactions.py, `Convection`), discretised like
+    `reaction_diffusion_1d_discretized`.  The term's operator G is the kernel finite-difference gradient on the mesh's own
+    neighbour sets (`gradient_stencil_size` points, interior and boundary rows alike); f and df come from the term, and
+    `pde.reaction` lets the solver linearise on the device.  E_sqrtm stays the Laplacian's: the uncertainty of G's weights is
+    not modelled."""
+    if bbox is None:
+        bbox = [0.0, 1.0]
+    bbox = np.asarray(bbox, dtype=np.float64)
+    if y0_fun is None:
+        y0_fun = sin_bell_1d
+    cls = {"dirichlet": problems.SemiLinearEvolutionDirichlet, "neumann": problems.SemiLinearEvolutionNeumann}.get(bcond)
+    if cls is None:
+        raise ValueError
+    f, df, df_diagonal = term.callables()
+    pde = cls(t0=t0, tmax=tmax, y0_fun=y0_fun, bbox=bbox, diffop=diffops.laplace(), diffop_scale=diffusion_rate,
+              f=f, df=df, df_diagonal=df_diagonal)
+    pde.reaction = term
+    mesh_spatial = mesh.RectangularMesh.from_bbox_1d(pde.bbox, step=dx)
+    if kernel is None:
+        kernel = kernels.SquareExponential()
+    pde.discretize(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
+                   stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
+    G, _ = discretize.fd_probabilistic(diffops.gradient(), mesh_spatial=mesh_spatial, kernel=kernel,
+                                       stencil_size_interior=gradient_stencil_size,
+                                       stencil_size_boundary=gradient_stencil_size, nugget_gram_matrix=nugget_gram_matrix_fd)
+    term.set_operator(G)
+    return pde
+
+
+def burgers_1d_discretized(viscosity=0.02, **kwargs):
+    """Viscous Burgers u_t = viscosity u_xx - u u_x: `convection_diffusion_1d_discretized` with `reactions.burgers()`."""
+    return convection_diffusion_1d_discretized(reactions.burgers(), diffusion_rate=viscosity, **kwargs)
 
 
 def reaction_diffusion_system_1d_discretized(reaction, *, diffusion_rates, y0_fun, bbox=None, t0=0.0, tmax=10.0, dx=0.05,

@@ -11,6 +11,9 @@ r' = P' + (A' B - A B') / B^2), in the kernel's order of operations.
 
 `SystemReaction` (further down) is the coupled form for up to four species on one mesh -- Lotka-Volterra, SIR, Gray-Scott --,
 handed over by `pnmol_filter_set_reaction_system` and linearised by k_linearize_system.
+
+`Convection` is a Burgers-type term c(u) (G u) + r(u) with a stencil operator G -- viscous Burgers, Burgers-Fisher --, handed
+over by `pnmol_filter_set_convection` and linearised by k_linearize_convection.
 """
 
 import ctypes
@@ -33,14 +36,14 @@ class ReactionDesc(ctypes.Structure):
     ]
 
 
-def _coefficients(name, c):
+def _coefficients(name, c, who="Reaction"):
     c = np.atleast_1d(np.asarray(c, dtype=np.float64))
     if c.ndim != 1:
-        raise ValueError(f"Reaction: {name} must be a 1-d sequence of scalar coefficients, got shape {c.shape}")
+        raise ValueError(f"{who}: {name} must be a 1-d sequence of scalar coefficients, got shape {c.shape}")
     if c.size > MAXDEG + 1:
-        raise ValueError(f"Reaction: {name} has degree {c.size - 1}, the largest supported is {MAXDEG}")
+        raise ValueError(f"{who}: {name} has degree {c.size - 1}, the largest supported is {MAXDEG}")
     if not np.all(np.isfinite(c)):
-        raise ValueError(f"Reaction: {name} has a coefficient that is not finite")
+        raise ValueError(f"{who}: {name} has a coefficient that is not finite")
     return tuple(float(x) for x in c)
 
 
@@ -127,6 +130,144 @@ class Reaction:
         if desc.deg_a < 0 and desc.deg_b < 0:
             return cls(p=p)
         return cls(p=p, a=tuple(desc.a[: desc.deg_a + 1]), b=tuple(desc.b[: desc.deg_b + 1]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Convection terms: f(u)_i = c(u_i) (G u)_i + r(u_i) with a stencil operator G (a discretised gradient) -- viscous Burgers,
+# Burgers-Fisher, advection-reaction (`pnmol_filter_set_convection`, k_linearize_convection).  The Jacobian
+# diag(c) G + diag(c' G u + r') is not diagonal: the linearisation rewrites every entry of a stencil row.
+
+
+class ConvectionDesc(ctypes.Structure):
+    """`pnmol_convection` of include/pnmol_hip.h."""
+
+    _fields_ = [("deg_c", ctypes.c_int), ("c", ctypes.c_double * (MAXDEG + 1)), ("r", ReactionDesc)]
+
+
+class Convection:
+    """f(u)_i = c(u_i) (G u)_i + r(u_i): `speed` holds the coefficients of c in ascending powers (scalars, the same at every
+    mesh point; degree <= 7), `reaction` is an optional `Reaction` r.  The (d, d) stencil matrix G belongs to a mesh: the problem
+    recipe (`pde.examples.convection_diffusion_1d_discretized`) sets it with `set_operator`.
+
+    `linearization` is the host form of the device arithmetic, in its order of operations (every operation rounded on its own):
+    g = G u summed over the non-zero entries of each row of G in ascending column order, starting from the first product; c, c',
+    r, r' by Horner; q = c' g + r' (c' g alone without a reaction); off-diagonal entries L_ij + c_i G_ij, the diagonal entry
+    (L_ii + c_i G_ii) + q_i; shift q u - r (the c g terms of J u - f cancel and are never formed)."""
+
+    def __init__(self, speed, reaction=None):
+        if np.size(speed) == 0:
+            raise ValueError("Convection: speed is empty; a term without convection is a Reaction")
+        self.speed = _coefficients("speed", speed, who="Convection")
+        if reaction is not None and not isinstance(reaction, Reaction):
+            raise TypeError(f"Convection: reaction must be a Reaction or None, got {type(reaction).__name__}")
+        self.reaction = reaction
+        self._G = None
+        self._ell = None
+
+    def __repr__(self):
+        shape = None if self._G is None else self._G.shape
+        return f"Convection(speed={self.speed!r}, reaction={self.reaction!r}, G={shape})"
+
+    # ------------------------------------------------------------------ the discretised operator
+    @property
+    def G(self):
+        return self._G
+
+    def set_operator(self, G):
+        """The stencil matrix G, (d, d): kept with its rows in compressed form (non-zero entries in ascending column order)."""
+        G = np.array(G, dtype=np.float64)
+        if G.ndim != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"Convection: G must be a square matrix, got shape {G.shape}")
+        if not np.all(np.isfinite(G)):
+            raise ValueError("Convection: G has an entry that is not finite")
+        d = G.shape[0]
+        nz = G != 0.0
+        count = nz.sum(axis=1)
+        w = int(count.max()) if d else 0
+        cols, vals = np.zeros((d, w), dtype=np.intp), np.zeros((d, w))
+        for i in range(d):
+            k = np.flatnonzero(nz[i])
+            cols[i, :k.size], vals[i, :k.size] = k, G[i, k]
+        self._G, self._ell = G, (cols, vals, count)
+        return self
+
+    def _has_reaction(self):
+        return self.reaction is not None and (len(self.reaction.p) > 0 or self.reaction.a is not None)
+
+    # ------------------------------------------------------------------ host arithmetic (the kernel's, in its order)
+    def _state(self, u):
+        if self._G is None:
+            raise ValueError("Convection: no operator G yet (set_operator; the problem recipes set it)")
+        u = np.asarray(u, dtype=np.float64)
+        if u.shape != (self._G.shape[0],):
+            raise ValueError(f"Convection: expected a vector of {self._G.shape[0]} entries, got shape {u.shape}")
+        return u
+
+    def _gradient(self, u):
+        cols, vals, count = self._ell
+        g = np.zeros_like(u)
+        for e in range(cols.shape[1]):
+            prod = vals[:, e] * u[cols[:, e]]
+            g = np.where(e < count, prod if e == 0 else g + prod, g)
+        return g
+
+    def _parts(self, u):
+        """(g, c, q, r) at u."""
+        g = self._gradient(u)
+        c, dc = _horner(self.speed, u)
+        q = dc * g
+        if self._has_reaction():
+            r, dr = self.reaction._value_and_derivative(u)
+            return g, c, q + dr, r
+        return g, c, q, np.zeros_like(u)
+
+    def value(self, u):
+        """f(u) = c(u) (G u) + r(u)."""
+        g, c, _, r = self._parts(self._state(u))
+        return c * g + r if self._has_reaction() else c * g
+
+    def linearization(self, u, L=None):
+        """(J_rows, shift) of the EK1 linearisation at u: J_rows is the dense (d, d) matrix diag(c) G + diag(q) -- with `L` given,
+        the operator M = L + J, formed entry by entry in the documented order -- and shift = q u - r = J u - f(u)."""
+        u = self._state(u)
+        _, c, q, r = self._parts(u)
+        rows = c[:, None] * self._G
+        if L is not None:
+            L = np.asarray(L, dtype=np.float64)
+            if L.shape != self._G.shape:
+                raise ValueError(f"Convection: L has shape {L.shape}, G has shape {self._G.shape}")
+            rows = L + rows
+        idx = np.arange(u.size)
+        rows[idx, idx] = rows[idx, idx] + q
+        return rows, q * u - r
+
+    def callables(self):
+        """(f(t, u), df(t, u) as a dense matrix, None): what the problem classes take."""
+        def f(_t, u):
+            return self.value(u)
+
+        def df(_t, u):
+            return self.linearization(u)[0]
+
+        return f, df, None
+
+    # ------------------------------------------------------------------ C ABI
+    def to_ctypes(self):
+        desc = ConvectionDesc()
+        desc.deg_c = len(self.speed) - 1
+        for k, c in enumerate(self.speed):
+            desc.c[k] = c
+        if self.reaction is not None:
+            desc.r = self.reaction.to_ctypes()
+        else:
+            desc.r.deg_p = desc.r.deg_a = desc.r.deg_b = -1
+        return desc
+
+    @classmethod
+    def from_ctypes(cls, desc):
+        r = desc.r
+        absent = r.deg_p < 0 and r.deg_a < 0 and r.deg_b < 0
+        return cls(tuple(desc.c[: desc.deg_c + 1]), None if absent else Reaction.from_ctypes(r))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -340,6 +481,16 @@ def gray_scott(feed, kill):
 def logistic(rate=1.0):
     """Fisher-KPP / logistic growth: rate * u (1 - u)."""
     return Reaction(p=(0.0, rate, -rate))
+
+
+def burgers():
+    """The convection term of viscous Burgers, u_t = kappa u_xx - u u_x: c(u) = -u."""
+    return Convection((0.0, -1.0))
+
+
+def burgers_fisher(rate=1.0):
+    """Burgers-Fisher, u_t = kappa u_xx - u u_x + rate u (1 - u): `burgers` with the logistic reaction."""
+    return Convection((0.0, -1.0), reaction=logistic(rate))
 
 
 def allen_cahn():

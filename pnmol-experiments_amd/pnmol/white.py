@@ -494,6 +494,13 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
 
     @staticmethod
     def _linearize(pde, m_at, t):
+        from .pde.reactions import Convection
+
+        term = getattr(pde, "reaction", None)
+        if isinstance(term, Convection) and pde.L.shape[0] == pde.L.shape[1]:
+            # the structured host form (operator entries and shift in the device's order of operations, no dense J_x @ m):
+            # the host route and the device route then produce the same operator and shift
+            return term.linearization(m_at, L=pde.L)
         fx = np.asarray(pde.f(t, m_at), dtype=np.float64)
         Jx = np.asarray(pde.df(t, m_at), dtype=np.float64)
         return pde.L + Jx, Jx @ m_at - fx
@@ -506,8 +513,9 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return None
         return np.asarray(dfd(t, m_at), dtype=np.float64)
 
-    # A problem with a `reaction` attribute (pde/reactions.py, a scalar `Reaction` or a coupled `SystemReaction`;
-    # `pde.examples.reaction_diffusion_1d_discretized`, `reaction_diffusion_system_1d_discretized`) is linearised on
+    # A problem with a `reaction` attribute (pde/reactions.py, a scalar `Reaction`, a coupled `SystemReaction` or a `Convection`
+    # term; `pde.examples.reaction_diffusion_1d_discretized`, `reaction_diffusion_system_1d_discretized`,
+    # `convection_diffusion_1d_discretized`) is linearised on
     # the device: `attempt_step` takes no host round trip and `solve_marginals` runs.  False: the host callables, as for
     # every other semilinear problem.  fp64 covariance-form white-noise solvers only; the others use the callables.
     reaction_on_device = True
