@@ -3459,7 +3459,7 @@ enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 // The loop is not fused while a reaction is set: the fused loop makes the next step's z and G inside the previous step's
 // k_readout launch, before that step's re-linearisation could run.
 inline bool fused_loop(const pnmol_filter* f) {
-    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !f->has_reaction;
+    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f);
 }
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
@@ -3641,7 +3641,7 @@ int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double 
 // (k_linearize, pnmol_reaction.hip)
 int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
               double* varout, StepKind kind) {
-    if (f->has_reaction) {
+    if (has_term(f)) {
         if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt)) return rc;
     }
     return dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind);
@@ -3824,6 +3824,34 @@ int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
 }  // namespace
 
 void pnmol_drop_graphs(pnmol_filter* f) { drop_graphs(f); }
+
+int pnmol_ell_reserve(pnmol_filter* f, int w) {
+    if (w <= f->ell_cap) return 0;
+    if (f->ell_col) (void)hipFree(f->ell_col);
+    if (f->ell_val) (void)hipFree(f->ell_val);
+    f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0, f->ellw = 0, f->ell_is_base = 0;
+    HIPCHK(f->ctx, hipMalloc(&f->ell_col, sizeof(int) * (size_t)w * f->mp));
+    HIPCHK(f->ctx, hipMalloc(&f->ell_val, sizeof(double) * (size_t)w * f->mp));
+    f->ell_cap = w;
+    return 0;
+}
+
+int pnmol_ell_restore_base(pnmol_filter* f, bool for_term) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const int mp = f->mp;
+    const bool columns = !f->ell_is_base || f->ellw != f->base_w;  // (ell_is_base implies the base width)
+    if (!columns && !for_term) return 0;
+    if (!for_term && f->ellw != f->base_w) drop_graphs(f);
+    if (int rc = pnmol_ell_reserve(f, f->base_w)) return rc;  // (only after a setter failed half-way)
+    if (columns)
+        HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->ell_col_base, sizeof(int) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->ell_val_base, sizeof(double) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
+    if (for_term) HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
+    f->ellw = f->base_w;
+    f->ell_is_base = 1;
+    return 0;
+}
 
 // ---- the sweep workspace of the callers outside the filter step (pnmol_internal.hpp) ---------------------------------------
 hipError_t sweep_ws_alloc(SweepWs* w, pnmol_ctx* ctx, int rt, int cb) {
@@ -4368,7 +4396,7 @@ int pnmol_filter_prepare_error_model(pnmol_filter* f, double dt) {
 int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double* shift_d) {
     if (!f || !M_dd) return -1;
     pnmol_ctx* ctx = f->ctx;
-    if (f->has_reaction) {
+    if (has_term(f)) {
         ctx->err = "pnmol_filter_set_operator: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
         return -1;
     }
@@ -4378,14 +4406,7 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
     const int w = build_ell(M_dd, f->hB.data(), f->d, f->ds, f->nB, f->mp, ecol, eval);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pageable host buffers: the copies below are synchronous anyway)
     if (w != f->ellw || w > f->ell_cap) drop_graphs(f);  // the stencil width / pointers are baked into captured launches
-    if (w > f->ell_cap) {
-        if (f->ell_col) (void)hipFree(f->ell_col);
-        if (f->ell_val) (void)hipFree(f->ell_val);
-        f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0;
-        HIPCHK(ctx, hipMalloc(&f->ell_col, sizeof(int) * ecol.size()));
-        HIPCHK(ctx, hipMalloc(&f->ell_val, sizeof(double) * eval.size()));
-        f->ell_cap = w;
-    }
+    if (int rc = pnmol_ell_reserve(f, w)) return rc;
     f->ellw = w;
     f->ell_is_base = 0;
     HIPCHK(ctx, hipMemcpy(f->ell_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
@@ -4399,7 +4420,7 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
 int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, const double* shift_d) {
     if (!f || !jdiag_d) return -1;
     pnmol_ctx* ctx = f->ctx;
-    if (f->has_reaction) {
+    if (has_term(f)) {
         ctx->err = "pnmol_filter_set_operator_diagonal: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
         return -1;
     }
@@ -4414,16 +4435,10 @@ int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, c
     const int d = f->d, mp = f->mp;
     std::memcpy(f->h_op, jdiag_d, sizeof(double) * d);
     for (int i = 0; i < mp; ++i) f->h_op[d + i] = (shift_d && i < d) ? shift_d[i] : 0.0;
-    if (!f->ell_is_base) {  // a dense pnmol_filter_set_operator came in between: back to the base image, whatever its width
-        // (a dense M of L's width can hold other off-diagonal values, or -- build_ell drops exact zeros -- another row pattern
-        // that moves the diagonal out of ell_diag_slot).  The copies go into the same buffers: captured graphs stay valid
-        // unless the width changes.
-        if (f->ellw != f->base_w) drop_graphs(f);
-        HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->ell_col_base, sizeof(int) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->ell_val_base, sizeof(double) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
-        f->ellw = f->base_w;
-        f->ell_is_base = 1;
-    }
+    // after a dense pnmol_filter_set_operator: back to the base image, whatever its width (a dense M of L's width can hold other
+    // off-diagonal values, or -- build_ell drops exact zeros -- another row pattern that moves the diagonal out of ell_diag_slot).
+    // The copies go into the same buffers: captured graphs stay valid unless the width changes.
+    if (int rc = pnmol_ell_restore_base(f, false)) return rc;
     k_operator_diagonal<<<(unsigned)((mp + 255) / 256), 256, 0, st>>>(f->ell_val, f->ell_val_base, f->ell_diag_slot, f->h_op_dev,
                                                                        f->shift, d, mp);
     HIPCHK(ctx, hipEventRecord(f->ev_op, st));
@@ -4764,7 +4779,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     if (rc != 0) return rc;
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
-    if (f->has_reaction) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
+    if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
     double frame = s->frame_dt;

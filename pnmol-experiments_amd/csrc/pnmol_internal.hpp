@@ -80,6 +80,20 @@ struct ObserveWs {
     std::vector<double> host;
 };
 
+enum class TermKind { none, scalar, system, convection };
+// The device image of a term that widens the stencil (pnmol_term_image.hpp): the creation-time operator with a slot for every
+// entry the linearisation writes -- w wide; columns, -L's values (0 in an added slot), for a convection term G's value per slot --
+// and the (slot_rows, mp) table of the same-point (system) or diagonal (convection) slots.  kind none: no image.
+struct TermImage {
+    int* col = nullptr;
+    double* val = nullptr;
+    double* g = nullptr;
+    int* slot = nullptr;
+    int w = 0, slot_rows = 0;
+    TermKind kind = TermKind::none;  // what it was built for
+    int ncomp = 0;
+};
+
 struct pnmol_filter {
     pnmol_ctx* ctx = nullptr;
     int d = 0, n = 0, nu = 0, nB = 0, m = 0, dp = 0, mp = 0, CB = 0, RBS = 0, RBW = 0, RT = 0, ellw = 0;
@@ -170,30 +184,20 @@ struct pnmol_filter {
     struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
     // Measurement updates (pnmol_state_observe): one workspace per padded column count, allocated on first use
     std::vector<ObserveWs*> ob_ws;
-    // Pointwise reaction term evaluated on the device (pnmol_filter_set_reaction; pnmol_reaction.hip).  While one is set the
-    // constant-step loop re-linearises in front of every step, runs non-fused and carries no error model.
-    bool has_reaction = false;
+    // The nonlinear term the device linearises itself (pnmol_reaction.hip): none, a pointwise reaction (pnmol_filter_set_reaction),
+    // a coupled system (pnmol_filter_set_reaction_system) or a convection term (pnmol_filter_set_convection), with the descriptor of
+    // that kind.  While one is set the constant-step loop re-linearises in front of every step, runs non-fused and carries no error
+    // model.  `term` changes at the end of a setter that succeeded; a setter that fails leaves TermKind::none on the base operator.
+    TermKind term = TermKind::none;
     pnmol_reaction reaction{};
-    // ... or a coupled system of sys.ncomp species (pnmol_filter_set_reaction_system), has_reaction with sys_set: the widened
-    // image of the creation-time operator (every PDE row has a slot for each of its ncomp same-point columns; sys_w wide, built
-    // for sys_img_ncomp species, 0 = none yet) and the (ncomp, mp) table of those slots
-    bool sys_set = false;
     pnmol_reaction_system sys{};
-    int* sys_col = nullptr;
-    double* sys_val = nullptr;
-    int* sys_slot = nullptr;
-    int sys_w = 0, sys_img_ncomp = 0;
-    // ... or a convection term c(u) . (G u) + r(u) (pnmol_filter_set_convection), has_reaction with cv_set: the union image of the
-    // creation-time operator and G (cv_w wide; columns, -L's values, G's value per slot, 0 where only L has an entry) and the
-    // slot of every PDE row's diagonal entry in it.  Rebuilt by every set call (G comes with the term).
-    bool cv_set = false;
     pnmol_convection cv{};
-    int* cv_col = nullptr;
-    double* cv_val = nullptr;
-    double* cv_g = nullptr;
-    int* cv_slot = nullptr;
-    int cv_w = 0;
+    // A filter holds one term, so it owns one image.  A system set again with the same ncomp reuses it (clearing and a scalar
+    // reaction leave it alone); a convection term rebuilds it with every set call (G comes with the term), and so does a system set
+    // after a convection term -- one more cold setter call than when each kind kept an image of its own.
+    TermImage term_img;
 };
+inline bool has_term(const pnmol_filter* f) { return f->term != TermKind::none; }
 
 struct pnmol_state {
     pnmol_filter* f = nullptr;
@@ -273,10 +277,18 @@ void pnmol_reaction_free_ws(pnmol_filter* f);
 // pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system, k_linearize_convection for a convection
 // term) on the ctx stream for one step over dt from the mean `mean` (Dp, in the frame frame_dt; 0 = raw coordinates): the
 // diagonal (same-point; for a convection term all) slots of ell_val and the shift become those of the EK1 linearisation of the
-// term at the predicted mean.  Needs f->has_reaction; no synchronisation.  -2: the launch failed.
+// term at the predicted mean.  Needs has_term(f); no synchronisation.  -2: the launch failed.
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);
+// pnmol_hip.hip: make ell_col / ell_val at least w slots wide.  Growing frees them (ellw = 0 until the caller has filled them): the
+// caller has dropped the graphs and knows the stream idle.
+int pnmol_ell_reserve(pnmol_filter* f, int w);
+// pnmol_hip.hip: the image of the operator given at creation back into ell_col / ell_val, on the ctx stream.  For a term setter
+// (for_term) the values are copied even over the base columns (k_linearize patches diagonal slots in place) and the shift is zeroed;
+// pnmol_filter_set_operator_diagonal writes diagonal slots and shift itself, so nothing happens while ell_is_base, and a change of
+// width drops the captured graphs.
+int pnmol_ell_restore_base(pnmol_filter* f, bool for_term);
 
 // The RTS smoother step (pnmol_smoother_step; pnmol_smooth.hip).
 constexpr int SM_MAXN = 4;

@@ -10,26 +10,43 @@
 //
 // Coupled systems of C <= 4 species (`pnmol_filter_set_reaction_system`; Lotka-Volterra, SIR): r_c depends on all species at the
 // same mesh point, so row c N + j of the Jacobian has C entries, at the columns k N + j.  The setter widens the stencil image
-// of L by those columns once (build_system_image), and k_linearize_system patches the C same-point slots of every row.
+// of L by those columns once (system_term_image), and k_linearize_system patches the C same-point slots of every row.
 //
 // Convection terms (`pnmol_filter_set_convection`; viscous Burgers, Burgers-Fisher): f(u)_i = c(u_i) (G u)_i + r(u_i) with a
 // stencil operator G.  The Jacobian diag(c) G + diag(c' G u + r') touches every entry of a stencil row, so the setter builds the
-// union image of L and G with G's value beside every slot (build_convection_image) and k_linearize_convection rewrites all slots
+// union image of L and G with G's value beside every slot (convection_term_image) and k_linearize_convection rewrites all slots
 // of a row; the shift (c' g + r') u - r needs no product with G (the c g terms of J u - f cancel).
+//
+// The three kinds share the predicted value and the rational evaluation on the device, and one image (pnmol_term_image.hpp), one
+// capability check and one installer (install_term) on the host; a filter holds one term (pnmol_filter::term).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_term_image.hpp"
 
 namespace {
 
-struct LinearizeArgs {
-    pnmol_reaction r;
+// what a kernel needs to form the predicted mean from the step's input mean
+struct Frame {
     double c[MAXN];  // A1[0][a] * ts[a]: row 0 of the transition times the frame change of the input mean
     double s0;       // raw-coordinate scale of derivative 0 in the frame of dt
 };
+template <class Descriptor>
+struct LinearizeArgs {
+    Descriptor t;
+    Frame fr;
+};
+
+// derivative 0 of the predicted mean at state component j, in raw coordinates: the arithmetic of pnmol_filter_predict_mean
+__device__ __forceinline__ double predicted_value(const Frame& fr, int n, const double* __restrict__ mean, int dp, int j) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int q = 0; q < n; ++q) acc = acc + fr.c[q] * mean[(long)q * dp + j];
+    return fr.s0 * acc;
+}
 
 // value and derivative of a polynomial (ascending coefficients, degree deg; deg < 0: absent, both zero), by Horner
 __device__ inline void horner(const double* __restrict__ c, int deg, double u, double& v, double& dv) {
@@ -43,9 +60,23 @@ __device__ inline void horner(const double* __restrict__ c, int deg, double u, d
     for (int k = deg - 1; k >= 1; --k) dv = dv * u + k * c[k];
 }
 
+// r = P + A / B and r' = P' + (A' B - A B') / B^2 at u (without a rational part: P and P')
+__device__ __forceinline__ void eval_reaction(const pnmol_reaction& t, double u, double& r, double& dr) {
+#pragma clang fp contract(off)
+    double P, dP, A, dA, B, dB;
+    horner(t.p, t.deg_p, u, P, dP);
+    r = P, dr = dP;
+    if (t.deg_a >= 0) {
+        horner(t.a, t.deg_a, u, A, dA);
+        horner(t.b, t.deg_b, u, B, dB);
+        r = P + A / B;
+        dr = dP + (dA * B - A * dB) / (B * B);
+    }
+}
+
 // One thread per measurement row.  Every operation is rounded on its own (no contraction into fused multiply-adds): the
 // results are those of the same formulas in NumPy (pnmol/pde/reactions.py), bit for bit.
-__global__ __launch_bounds__(256) void k_linearize(LinearizeArgs a, int n, const double* __restrict__ mean,
+__global__ __launch_bounds__(256) void k_linearize(LinearizeArgs<pnmol_reaction> a, int n, const double* __restrict__ mean,
                                                    double* __restrict__ ell_val, const double* __restrict__ base_val,
                                                    const int* __restrict__ slot, double* __restrict__ shift, int d, int dp,
                                                    int mp) {
@@ -56,30 +87,15 @@ __global__ __launch_bounds__(256) void k_linearize(LinearizeArgs a, int n, const
         shift[i] = 0.0;
         return;
     }
-    double acc = 0.0;
-    for (int q = 0; q < n; ++q) acc = acc + a.c[q] * mean[(long)q * dp + i];
-    const double u = a.s0 * acc;
-    double P, dP, A, dA, B, dB;
-    horner(a.r.p, a.r.deg_p, u, P, dP);
-    double r = P, dr = dP;
-    if (a.r.deg_a >= 0) {
-        horner(a.r.a, a.r.deg_a, u, A, dA);
-        horner(a.r.b, a.r.deg_b, u, B, dB);
-        r = P + A / B;
-        dr = dP + (dA * B - A * dB) / (B * B);
-    }
+    const double u = predicted_value(a.fr, n, mean, dp, i);
+    double r, dr;
+    eval_reaction(a.t, u, r, dr);
     const long e = (long)slot[i] * mp + i;
     ell_val[e] = base_val[e] - dr;
     shift[i] = dr * u - r;
 }
 
 // ---- coupled systems: r_c(u) = P_c(u) + A_c(u) / B_c(u) of the C species at one mesh point (pnmol_filter_set_reaction_system)
-struct LinearizeSystemArgs {
-    pnmol_reaction_system r;
-    double c[MAXN];  // as in LinearizeArgs
-    double s0;
-};
-
 constexpr int SC = PNMOL_SYSTEM_MAXCOMP;
 
 // coef * u_0^pw[0] * u_1^pw[1] * ..., one multiplication at a time, species by species; `less` takes one factor off that species
@@ -126,10 +142,10 @@ __device__ __forceinline__ void poly_eval(const pnmol_system_poly& p, const doub
 
 // One thread per measurement row i = c N + j: the C species at point j, r_c and its C partial derivatives, the C same-point slots
 // of the row and its shift.  Every operation is rounded on its own, in the order of SystemReaction (pnmol/pde/reactions.py).
-__global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a, int n, int N, const double* __restrict__ mean,
-                                                          double* __restrict__ ell_val, const double* __restrict__ base_val,
-                                                          const int* __restrict__ slot, double* __restrict__ shift, int d,
-                                                          int dp, int mp) {
+__global__ __launch_bounds__(256) void k_linearize_system(LinearizeArgs<pnmol_reaction_system> a, int n, int N,
+                                                          const double* __restrict__ mean, double* __restrict__ ell_val,
+                                                          const double* __restrict__ base_val, const int* __restrict__ slot,
+                                                          double* __restrict__ shift, int d, int dp, int mp) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= mp) return;
@@ -137,18 +153,11 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a,
         shift[i] = 0.0;
         return;
     }
-    const int C = a.r.ncomp;
+    const int C = a.t.ncomp;
     const int c = i / N, j = i - c * N;
     double u[SC];
 #pragma unroll
-    for (int k = 0; k < SC; ++k) {
-        u[k] = 0.0;
-        if (k < C) {
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = acc + a.c[q] * mean[(long)q * dp + (long)k * N + j];
-            u[k] = a.s0 * acc;
-        }
-    }
+    for (int k = 0; k < SC; ++k) u[k] = k < C ? predicted_value(a.fr, n, mean, dp, k * N + j) : 0.0;
     double r = 0.0, J[SC];
 #pragma unroll
     for (int k = 0; k < SC; ++k) J[k] = 0.0;
@@ -158,14 +167,14 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a,
     for (int cc = 0; cc < SC; ++cc) {
         if (cc == c) {
             double P, dP[SC];
-            poly_eval(a.r.p[cc], u, P, dP);
+            poly_eval(a.t.p[cc], u, P, dP);
             r = P;
 #pragma unroll
             for (int k = 0; k < SC; ++k) J[k] = dP[k];
-            if (a.r.a[cc].nterms > 0) {
+            if (a.t.a[cc].nterms > 0) {
                 double A, dA[SC], B, dB[SC];
-                poly_eval(a.r.a[cc], u, A, dA);
-                poly_eval(a.r.b[cc], u, B, dB);
+                poly_eval(a.t.a[cc], u, A, dA);
+                poly_eval(a.t.b[cc], u, B, dB);
                 r = P + A / B;
 #pragma unroll
                 for (int k = 0; k < SC; ++k) J[k] = dP[k] + (dA[k] * B - A * dB[k]) / (B * B);
@@ -185,27 +194,12 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeSystemArgs a,
 }
 
 // ---- convection terms: f(u)_i = c(u_i) (G u)_i + r(u_i) (pnmol_filter_set_convection)
-struct LinearizeConvectionArgs {
-    pnmol_convection t;
-    double c[MAXN];  // as in LinearizeArgs
-    double s0;
-};
-
-// derivative 0 of the predicted mean at mesh point j, in raw coordinates: k_linearize's arithmetic
-__device__ __forceinline__ double predicted_value(const double (&c)[MAXN], double s0, int n, const double* __restrict__ mean,
-                                                  int dp, int j) {
-#pragma clang fp contract(off)
-    double acc = 0.0;
-    for (int q = 0; q < n; ++q) acc = acc + c[q] * mean[(long)q * dp + j];
-    return s0 * acc;
-}
-
 // One thread per measurement row i: u_i and the u of the row's slot columns (recomputed per slot: one launch, no grid-wide
 // dependency), g_i = (G u)_i over the entries of G that are not zero in slot (= ascending column) order starting from the first
 // product, c, c', r, r' by Horner, q = c' g + r'; every slot becomes base - c G, the diagonal one loses q as well, and the shift
 // is q u - r.  Every operation is rounded on its own, in the order of Convection.linearization (pnmol/pde/reactions.py).
 // img_col / img_val / img_g: the union image of the creation-time operator and G (w slots, packed to the front of every row).
-__global__ __launch_bounds__(256) void k_linearize_convection(LinearizeConvectionArgs a, int n, int w,
+__global__ __launch_bounds__(256) void k_linearize_convection(LinearizeArgs<pnmol_convection> a, int n, int w,
                                                               const double* __restrict__ mean, double* __restrict__ ell_val,
                                                               const int* __restrict__ img_col, const double* __restrict__ img_val,
                                                               const double* __restrict__ img_g, const int* __restrict__ slot,
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256) void k_linearize_convection(LinearizeConvectio
         shift[i] = 0.0;
         return;
     }
-    const double u = predicted_value(a.c, a.s0, n, mean, dp, i);
+    const double u = predicted_value(a.fr, n, mean, dp, i);
     double g = 0.0;
     bool first = true;
     for (int e = 0; e < w; ++e) {
@@ -225,20 +219,13 @@ __global__ __launch_bounds__(256) void k_linearize_convection(LinearizeConvectio
         if (col < 0) break;
         const double gv = img_g[(long)e * mp + i];
         if (gv == 0.0) continue;
-        const double prod = gv * predicted_value(a.c, a.s0, n, mean, dp, col);
+        const double prod = gv * predicted_value(a.fr, n, mean, dp, col);
         g = first ? prod : g + prod;
         first = false;
     }
-    double cu, dcu, P, dP, A, dA, B, dB;
+    double cu, dcu, r, dr;
     horner(a.t.c, a.t.deg_c, u, cu, dcu);
-    horner(a.t.r.p, a.t.r.deg_p, u, P, dP);
-    double r = P, dr = dP;
-    if (a.t.r.deg_a >= 0) {
-        horner(a.t.r.a, a.t.r.deg_a, u, A, dA);
-        horner(a.t.r.b, a.t.r.deg_b, u, B, dB);
-        r = P + A / B;
-        dr = dP + (dA * B - A * dB) / (B * B);
-    }
+    eval_reaction(a.t.r, u, r, dr);
     double q = dcu * g;
     if (a.t.r.deg_p >= 0 || a.t.r.deg_a >= 0) q = q + dr;
     const int ds = slot[i];
@@ -250,21 +237,6 @@ __global__ __launch_bounds__(256) void k_linearize_convection(LinearizeConvectio
         ell_val[at] = v;
     }
     shift[i] = q * u - r;
-}
-
-// the stencil rows of the operator given at creation and a zero shift (what pnmol_filter_set_operator_diagonal restores
-// after a dense upload), on the ctx stream
-int restore_base_operator(pnmol_filter* f) {
-    pnmol_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    const int mp = f->mp;
-    if (!f->ell_is_base || f->ellw != f->base_w)
-        HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->ell_col_base, sizeof(int) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->ell_val_base, sizeof(double) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
-    f->ellw = f->base_w;
-    f->ell_is_base = 1;
-    return 0;
 }
 
 bool all_finite(const double* c, int deg) {
@@ -316,159 +288,133 @@ const char* system_descriptor_fault(const pnmol_reaction_system* r) {
     return nullptr;
 }
 
-void free_system_image(pnmol_filter* f) {
-    for (void* q : {(void*)f->sys_col, (void*)f->sys_val, (void*)f->sys_slot})
-        if (q) (void)hipFree(q);
-    f->sys_col = nullptr, f->sys_val = nullptr, f->sys_slot = nullptr;
-    f->sys_w = 0, f->sys_img_ncomp = 0;
+// what every term setter asks of the filter once the descriptor is in order (`path`: what the filter lacks), or empty
+std::string capability_fault(const pnmol_filter* f, const char* path) {
+    if (f->ds != f->d) return std::string("a latent-force filter (d_state != d) has no ") + path;
+    if (f->p32) return std::string("an fp32 filter has no ") + path;
+    if (!f->base_has_diag) return "a row of the operator given at creation has no diagonal entry";
+    return {};
 }
 
-// The widened image of the operator given at creation for C species: every PDE row i = c N + j has a slot for each column
-// k N + j (the value of L there, or 0), slots in ascending column order as build_ell leaves them; boundary rows as they are.
-// Built on the host from the base image (read back once per C) and kept on the device beside the (C, mp) slot table.
-int build_system_image(pnmol_filter* f, int C) {
-    pnmol_ctx* ctx = f->ctx;
-    const int d = f->d, mp = f->mp, bw = f->base_w, N = d / C;
-    std::vector<int> bcol((size_t)bw * mp);
-    std::vector<double> bval((size_t)bw * mp);
-    HIPCHK(ctx, hipMemcpy(bcol.data(), f->ell_col_base, sizeof(int) * bcol.size(), hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(bval.data(), f->ell_val_base, sizeof(double) * bval.size(), hipMemcpyDeviceToHost));
-    std::vector<std::vector<std::pair<int, double>>> rows((size_t)mp);
-    int w = 1;
-    for (int i = 0; i < mp; ++i) {
-        auto& row = rows[i];
-        for (int e = 0; e < bw; ++e)
-            if (bcol[(size_t)e * mp + i] >= 0) row.emplace_back(bcol[(size_t)e * mp + i], bval[(size_t)e * mp + i]);
-        if (i < d) {
-            const int j = i % N;
-            for (int k = 0; k < C; ++k) {
-                const int col = k * N + j;
-                bool have = false;
-                for (const auto& cv : row) have = have || cv.first == col;
-                if (!have) row.emplace_back(col, 0.0);
-            }
-            std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& x, const std::pair<int, double>& y) {
-                return x.first < y.first;
-            });
-        }
-        w = std::max(w, (int)row.size());
-    }
-    std::vector<int> ecol((size_t)w * mp, -1), slot((size_t)C * mp, 0);
-    std::vector<double> eval((size_t)w * mp, 0.0);
-    for (int i = 0; i < mp; ++i)
-        for (int e = 0; e < (int)rows[i].size(); ++e) {
-            ecol[(size_t)e * mp + i] = rows[i][e].first;
-            eval[(size_t)e * mp + i] = rows[i][e].second;
-            if (i < d && rows[i][e].first % N == i % N) slot[(size_t)(rows[i][e].first / N) * mp + i] = e;
-        }
-    free_system_image(f);
-    HIPCHK(ctx, hipMalloc(&f->sys_col, sizeof(int) * ecol.size()));
-    HIPCHK(ctx, hipMalloc(&f->sys_val, sizeof(double) * eval.size()));
-    HIPCHK(ctx, hipMalloc(&f->sys_slot, sizeof(int) * slot.size()));
-    HIPCHK(ctx, hipMemcpy(f->sys_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(f->sys_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(f->sys_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
-    f->sys_w = w;
-    f->sys_img_ncomp = C;
+int refuse(pnmol_filter* f, const char* who, const std::string& why) {
+    f->ctx->err = std::string(who) + why;
+    return -1;
+}
+
+// the descriptor as the kernels take it: coefficients above a degree are zero
+void copy_canonical(pnmol_reaction* dst, const pnmol_reaction* r) {
+    std::memset(dst, 0, sizeof(*dst));
+    dst->deg_p = r->deg_p, dst->deg_a = r->deg_a, dst->deg_b = r->deg_b;
+    for (int k = 0; k <= r->deg_p; ++k) dst->p[k] = r->p[k];
+    for (int k = 0; k <= r->deg_a; ++k) dst->a[k] = r->a[k];
+    for (int k = 0; k <= r->deg_b; ++k) dst->b[k] = r->b[k];
+}
+
+void free_term_image(pnmol_filter* f) {
+    TermImage& im = f->term_img;
+    for (void* q : {(void*)im.col, (void*)im.val, (void*)im.g, (void*)im.slot})
+        if (q) (void)hipFree(q);
+    im = TermImage{};
+}
+
+template <class T>
+int upload(pnmol_ctx* ctx, T** dst, const std::vector<T>& src) {
+    if (src.empty()) return 0;
+    HIPCHK(ctx, hipMalloc(dst, sizeof(T) * src.size()));
+    HIPCHK(ctx, hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
-void free_convection_image(pnmol_filter* f) {
-    for (void* q : {(void*)f->cv_col, (void*)f->cv_val, (void*)f->cv_g, (void*)f->cv_slot})
-        if (q) (void)hipFree(q);
-    f->cv_col = nullptr, f->cv_val = nullptr, f->cv_g = nullptr, f->cv_slot = nullptr;
-    f->cv_w = 0;
-}
-
-// The union image of the operator given at creation and G (d x d, row major): every PDE row has a slot for each column in which
-// either has an entry (the value of -L there, or 0), slots in ascending column order as build_ell leaves them, and G's value
-// beside each slot; boundary rows as they are.  Built on the host from the base image and kept on the device beside the table
-// of the diagonal slots.  The caller has synchronised the stream: the buffers replaced here may have been read.
-int build_convection_image(pnmol_filter* f, const double* G) {
+// The filter's image for a system of ncomp species or a convection term with G: the base image read back, widened on the host
+// (pnmol_term_image.hpp) and kept on the device.  The caller has synchronised the stream: the image replaced here may have been
+// read.  The image names its kind only once it is complete.
+int build_image(pnmol_filter* f, TermKind kind, int ncomp, const double* G) {
     pnmol_ctx* ctx = f->ctx;
     const int d = f->d, mp = f->mp, bw = f->base_w;
     std::vector<int> bcol((size_t)bw * mp);
     std::vector<double> bval((size_t)bw * mp);
     HIPCHK(ctx, hipMemcpy(bcol.data(), f->ell_col_base, sizeof(int) * bcol.size(), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(bval.data(), f->ell_val_base, sizeof(double) * bval.size(), hipMemcpyDeviceToHost));
-    std::vector<std::vector<std::pair<int, double>>> rows((size_t)mp);
-    int w = 1;
-    for (int i = 0; i < mp; ++i) {
-        auto& row = rows[i];
-        for (int e = 0; e < bw; ++e)
-            if (bcol[(size_t)e * mp + i] >= 0) row.emplace_back(bcol[(size_t)e * mp + i], bval[(size_t)e * mp + i]);
-        if (i < d) {
-            for (int k = 0; k < d; ++k) {
-                if (G[(size_t)i * d + k] == 0.0) continue;
-                bool have = false;
-                for (const auto& cv : row) have = have || cv.first == k;
-                if (!have) row.emplace_back(k, 0.0);
-            }
-            std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& x, const std::pair<int, double>& y) {
-                return x.first < y.first;
-            });
-        }
-        w = std::max(w, (int)row.size());
-    }
-    std::vector<int> ecol((size_t)w * mp, -1), slot((size_t)mp, 0);
-    std::vector<double> eval((size_t)w * mp, 0.0), eg((size_t)w * mp, 0.0);
-    for (int i = 0; i < mp; ++i)
-        for (int e = 0; e < (int)rows[i].size(); ++e) {
-            const int col = rows[i][e].first;
-            ecol[(size_t)e * mp + i] = col;
-            eval[(size_t)e * mp + i] = rows[i][e].second;
-            if (i < d && col < d) eg[(size_t)e * mp + i] = G[(size_t)i * d + col];
-            if (i < d && col == i) slot[i] = e;
-        }
-    free_convection_image(f);
-    HIPCHK(ctx, hipMalloc(&f->cv_col, sizeof(int) * ecol.size()));
-    HIPCHK(ctx, hipMalloc(&f->cv_val, sizeof(double) * eval.size()));
-    HIPCHK(ctx, hipMalloc(&f->cv_g, sizeof(double) * eg.size()));
-    HIPCHK(ctx, hipMalloc(&f->cv_slot, sizeof(int) * slot.size()));
-    HIPCHK(ctx, hipMemcpy(f->cv_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(f->cv_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(f->cv_g, eg.data(), sizeof(double) * eg.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(f->cv_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
-    f->cv_w = w;
+    const TermImageHost h = kind == TermKind::system ? system_term_image(bcol, bval, bw, d, mp, ncomp)
+                                                     : convection_term_image(bcol, bval, bw, d, mp, G);
+    free_term_image(f);
+    TermImage& im = f->term_img;
+    if (int rc = upload(ctx, &im.col, h.col)) return rc;
+    if (int rc = upload(ctx, &im.val, h.val)) return rc;
+    if (int rc = upload(ctx, &im.g, h.g)) return rc;
+    if (int rc = upload(ctx, &im.slot, h.slot)) return rc;
+    im.w = h.w, im.slot_rows = (int)(h.slot.size() / mp), im.kind = kind, im.ncomp = ncomp;
     return 0;
+}
+
+// the image of a system or a convection term into ell_col / ell_val (grown if it is wider), and a zero shift
+int put_term_image(pnmol_filter* f, TermKind kind, int ncomp, const double* G) {
+    pnmol_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    const int mp = f->mp;
+    TermImage& im = f->term_img;
+    const bool reuse = kind == TermKind::system && im.kind == kind && im.ncomp == ncomp;
+    if (!reuse || im.w > f->ell_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(st));  // the buffers replaced below may still be read
+        if (!reuse)
+            if (int rc = build_image(f, kind, ncomp, G)) return rc;
+        if (int rc = pnmol_ell_reserve(f, im.w)) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_col, im.col, sizeof(int) * (size_t)im.w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, im.val, sizeof(double) * (size_t)im.w * mp, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
+    f->ellw = im.w;
+    f->ell_is_base = 0;  // (pnmol_ell_restore_base copies the columns back)
+    return 0;
+}
+
+// Make `kind` (none: clear) the filter's term; its descriptor is in place.  The descriptor travels by value in the captured
+// launches, width and pointers are baked in too, and the loop's launch sequence differs with and without a term: the graphs go.
+// A failure leaves no half-installed term: no image, no term, the operator given at creation.
+int install_term(pnmol_filter* f, TermKind kind, int ncomp = 0, const double* G = nullptr) {
+    pnmol_drop_graphs(f);
+    const bool image = kind == TermKind::system || kind == TermKind::convection;
+    const int rc = image ? put_term_image(f, kind, ncomp, G) : pnmol_ell_restore_base(f, true);
+    f->sq_dt = -1.0;  // the error model belongs to the operator that was set
+    f->term = rc ? TermKind::none : kind;
+    if (rc) {
+        const std::string err = f->ctx->err;
+        free_term_image(f);
+        (void)pnmol_ell_restore_base(f, true);
+        f->ctx->err = err;
+    }
+    return rc;
 }
 
 }  // namespace
 
-void pnmol_reaction_free_ws(pnmol_filter* f) {
-    free_system_image(f);
-    free_convection_image(f);
-}
+void pnmol_reaction_free_ws(pnmol_filter* f) { free_term_image(f); }
 
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt) {
-    double c[MAXN];
-    for (int q = 0; q < MAXN; ++q) c[q] = 0.0;
+    Frame fr;
+    for (int q = 0; q < MAXN; ++q) fr.c[q] = 0.0;
     for (int q = 0; q < f->n; ++q) {
         const double so = frame_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, q, frame_dt);
-        c[q] = f->iwp.A1[q] * (so / nordsieck_scale(f->nu, q, dt));
+        fr.c[q] = f->iwp.A1[q] * (so / nordsieck_scale(f->nu, q, dt));
     }
+    fr.s0 = nordsieck_scale(f->nu, 0, dt);
     const unsigned blocks = (unsigned)((f->mp + 255) / 256);
-    if (f->cv_set) {
-        LinearizeConvectionArgs a;
-        a.t = f->cv;
-        std::memcpy(a.c, c, sizeof(c));
-        a.s0 = nordsieck_scale(f->nu, 0, dt);
-        k_linearize_convection<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, f->cv_w, mean, f->ell_val, f->cv_col, f->cv_val,
-                                                                   f->cv_g, f->cv_slot, f->shift, f->d, f->dp, f->mp);
-    } else if (f->sys_set) {
-        LinearizeSystemArgs a;
-        a.r = f->sys;
-        std::memcpy(a.c, c, sizeof(c));
-        a.s0 = nordsieck_scale(f->nu, 0, dt);
-        k_linearize_system<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, f->d / f->sys.ncomp, mean, f->ell_val, f->sys_val,
-                                                               f->sys_slot, f->shift, f->d, f->dp, f->mp);
-    } else {
-        LinearizeArgs a;
-        a.r = f->reaction;
-        std::memcpy(a.c, c, sizeof(c));
-        a.s0 = nordsieck_scale(f->nu, 0, dt);
-        k_linearize<<<blocks, 256, 0, f->ctx->stream>>>(a, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot, f->shift,
-                                                        f->d, f->dp, f->mp);
+    hipStream_t st = f->ctx->stream;
+    const TermImage& im = f->term_img;
+    switch (f->term) {
+        case TermKind::none: return -1;
+        case TermKind::scalar:
+            k_linearize<<<blocks, 256, 0, st>>>({f->reaction, fr}, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot,
+                                                f->shift, f->d, f->dp, f->mp);
+            break;
+        case TermKind::system:
+            k_linearize_system<<<blocks, 256, 0, st>>>({f->sys, fr}, f->n, f->d / f->sys.ncomp, mean, f->ell_val, im.val, im.slot,
+                                                       f->shift, f->d, f->dp, f->mp);
+            break;
+        case TermKind::convection:
+            k_linearize_convection<<<blocks, 256, 0, st>>>({f->cv, fr}, f->n, im.w, mean, f->ell_val, im.col, im.val, im.g,
+                                                           im.slot, f->shift, f->d, f->dp, f->mp);
+            break;
     }
     HIPCHK(f->ctx, hipGetLastError());
     return 0;
@@ -481,78 +427,26 @@ int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r) {
     if (!f) return -1;
     pnmol_ctx* ctx = f->ctx;
     if (r) {
-        const char* why = reaction_descriptor_fault(r);
-        if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no pointwise reaction path";
-        if (!why && f->p32) why = "an fp32 filter has no pointwise reaction path";
-        if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
-        if (why) {
-            ctx->err = std::string(who) + why;
-            return -1;
-        }
+        const char* fault = reaction_descriptor_fault(r);
+        const std::string why = fault ? fault : capability_fault(f, "pointwise reaction path");
+        if (!why.empty()) return refuse(f, who, why);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!r && !f->has_reaction) return 0;
-    // the coefficients travel by value in the captured k_linearize launches, and the loop's launch sequence differs with and
-    // without a reaction
-    pnmol_drop_graphs(f);
-    if (int rc = restore_base_operator(f)) return rc;
-    f->sq_dt = -1.0;  // the error model belongs to the operator that was set
-    f->has_reaction = r != nullptr;
-    f->sys_set = false;  // (a filter holds one term of any kind)
-    f->cv_set = false;
-    if (r) {
-        std::memset(&f->reaction, 0, sizeof(f->reaction));
-        f->reaction.deg_p = r->deg_p, f->reaction.deg_a = r->deg_a, f->reaction.deg_b = r->deg_b;
-        for (int k = 0; k <= r->deg_p; ++k) f->reaction.p[k] = r->p[k];
-        for (int k = 0; k <= r->deg_a; ++k) f->reaction.a[k] = r->a[k];
-        for (int k = 0; k <= r->deg_b; ++k) f->reaction.b[k] = r->b[k];
-    }
-    return 0;
+    if (!r) return has_term(f) ? install_term(f, TermKind::none) : 0;  // NULL to any setter clears any kind
+    copy_canonical(&f->reaction, r);
+    return install_term(f, TermKind::scalar);
 }
 
 int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_system* r) {
     static const char* who = "pnmol_filter_set_reaction_system: ";
     if (!f) return -1;
-    if (!r) return pnmol_filter_set_reaction(f, nullptr);  // NULL to either setter clears either kind
+    if (!r) return pnmol_filter_set_reaction(f, nullptr);
     pnmol_ctx* ctx = f->ctx;
-    const char* why = system_descriptor_fault(r);
-    if (!why && f->d % r->ncomp != 0) why = "d is not a multiple of ncomp";
-    if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no pointwise reaction path";
-    if (!why && f->p32) why = "an fp32 filter has no pointwise reaction path";
-    if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
-    if (why) {
-        ctx->err = std::string(who) + why;
-        return -1;
-    }
+    const char* fault = system_descriptor_fault(r);
+    if (!fault && f->d % r->ncomp != 0) fault = "d is not a multiple of ncomp";
+    const std::string why = fault ? fault : capability_fault(f, "pointwise reaction path");
+    if (!why.empty()) return refuse(f, who, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int mp = f->mp;
-    pnmol_drop_graphs(f);  // the descriptor travels by value in the captured launches; width and pointers are baked in too
-    if (f->sys_img_ncomp != r->ncomp || f->sys_w > f->ell_cap) {
-        HIPCHK(ctx, hipStreamSynchronize(st));  // the buffers replaced below may still be read
-        if (f->sys_img_ncomp != r->ncomp)
-            if (int rc = build_system_image(f, r->ncomp)) {
-                free_system_image(f);
-                return rc;
-            }
-        if (f->sys_w > f->ell_cap) {
-            if (f->ell_col) (void)hipFree(f->ell_col);
-            if (f->ell_val) (void)hipFree(f->ell_val);
-            f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0, f->ellw = 0, f->ell_is_base = 0;
-            HIPCHK(ctx, hipMalloc(&f->ell_col, sizeof(int) * (size_t)f->sys_w * mp));
-            HIPCHK(ctx, hipMalloc(&f->ell_val, sizeof(double) * (size_t)f->sys_w * mp));
-            f->ell_cap = f->sys_w;
-        }
-    }
-    HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->sys_col, sizeof(int) * (size_t)f->sys_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->sys_val, sizeof(double) * (size_t)f->sys_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
-    f->ellw = f->sys_w;
-    f->ell_is_base = 0;  // (restore_base_operator copies the columns back)
-    f->sq_dt = -1.0;     // the error model belongs to the operator that was set
-    f->has_reaction = true;
-    f->sys_set = true;
-    f->cv_set = false;
     std::memset(&f->sys, 0, sizeof(f->sys));
     f->sys.ncomp = r->ncomp;
     for (int c = 0; c < r->ncomp; ++c) {
@@ -563,68 +457,30 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
             for (int t = 0; t < src[g]->nterms; ++t) dst[g]->term[t] = src[g]->term[t];
         }
     }
-    return 0;
+    return install_term(f, TermKind::system, r->ncomp);
 }
 
 int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, const double* G_dd) {
     static const char* who = "pnmol_filter_set_convection: ";
     if (!f) return -1;
-    if (!term) return pnmol_filter_set_reaction(f, nullptr);  // NULL to any setter clears any kind
+    if (!term) return pnmol_filter_set_reaction(f, nullptr);
     pnmol_ctx* ctx = f->ctx;
-    const char* why = nullptr;
-    if (!G_dd) why = "a convection term needs its operator G";
-    if (!why && (term->deg_c < -1 || term->deg_c > PNMOL_REACTION_MAXDEG)) why = "a degree outside [-1, 7]";
-    if (!why) why = reaction_descriptor_fault(&term->r);
-    if (!why && !all_finite(term->c, term->deg_c)) why = "a coefficient is not finite";
-    if (!why && f->ds != f->d) why = "a latent-force filter (d_state != d) has no convection path";
-    if (!why && f->p32) why = "an fp32 filter has no convection path";
-    if (!why && !f->base_has_diag) why = "a row of the operator given at creation has no diagonal entry";
-    if (!why)
-        for (size_t k = 0; k < (size_t)f->d * f->d && !why; ++k)
+    const char* fault = nullptr;
+    if (!G_dd) fault = "a convection term needs its operator G";
+    if (!fault && (term->deg_c < -1 || term->deg_c > PNMOL_REACTION_MAXDEG)) fault = "a degree outside [-1, 7]";
+    if (!fault) fault = reaction_descriptor_fault(&term->r);
+    if (!fault && !all_finite(term->c, term->deg_c)) fault = "a coefficient is not finite";
+    std::string why = fault ? fault : capability_fault(f, "convection path");
+    if (why.empty())
+        for (size_t k = 0; k < (size_t)f->d * f->d && why.empty(); ++k)
             if (!std::isfinite(G_dd[k])) why = "an entry of G is not finite";
-    if (why) {
-        ctx->err = std::string(who) + why;
-        return -1;
-    }
+    if (!why.empty()) return refuse(f, who, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int mp = f->mp;
-    pnmol_drop_graphs(f);  // the descriptor travels by value in the captured launches; width and pointers are baked in too
-    HIPCHK(ctx, hipStreamSynchronize(st));  // the image replaced below may still be read
-    f->cv_set = false;
-    if (int rc = build_convection_image(f, G_dd)) {
-        // no image: leave the filter without a term, on the operator given at creation
-        free_convection_image(f);
-        f->has_reaction = false, f->sys_set = false;
-        (void)restore_base_operator(f);
-        f->sq_dt = -1.0;
-        return rc;
-    }
-    if (f->cv_w > f->ell_cap) {
-        if (f->ell_col) (void)hipFree(f->ell_col);
-        if (f->ell_val) (void)hipFree(f->ell_val);
-        f->ell_col = nullptr, f->ell_val = nullptr, f->ell_cap = 0, f->ellw = 0, f->ell_is_base = 0;
-        HIPCHK(ctx, hipMalloc(&f->ell_col, sizeof(int) * (size_t)f->cv_w * mp));
-        HIPCHK(ctx, hipMalloc(&f->ell_val, sizeof(double) * (size_t)f->cv_w * mp));
-        f->ell_cap = f->cv_w;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->cv_col, sizeof(int) * (size_t)f->cv_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->cv_val, sizeof(double) * (size_t)f->cv_w * mp, hipMemcpyDeviceToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
-    f->ellw = f->cv_w;
-    f->ell_is_base = 0;  // (restore_base_operator copies the columns back)
-    f->sq_dt = -1.0;     // the error model belongs to the operator that was set
-    f->has_reaction = true;
-    f->sys_set = false;
-    f->cv_set = true;
     std::memset(&f->cv, 0, sizeof(f->cv));
     f->cv.deg_c = term->deg_c;
     for (int k = 0; k <= term->deg_c; ++k) f->cv.c[k] = term->c[k];
-    f->cv.r.deg_p = term->r.deg_p, f->cv.r.deg_a = term->r.deg_a, f->cv.r.deg_b = term->r.deg_b;
-    for (int k = 0; k <= term->r.deg_p; ++k) f->cv.r.p[k] = term->r.p[k];
-    for (int k = 0; k <= term->r.deg_a; ++k) f->cv.r.a[k] = term->r.a[k];
-    for (int k = 0; k <= term->r.deg_b; ++k) f->cv.r.b[k] = term->r.b[k];
-    return 0;
+    copy_canonical(&f->cv.r, &term->r);
+    return install_term(f, TermKind::convection, 0, G_dd);
 }
 
 int pnmol_filter_linearize(pnmol_filter* f, const pnmol_state* in, double dt) {
@@ -634,10 +490,7 @@ int pnmol_filter_linearize(pnmol_filter* f, const pnmol_state* in, double dt) {
         return -1;
     }
     pnmol_ctx* ctx = f->ctx;
-    if (!f->has_reaction) {
-        ctx->err = std::string(who) + "no reaction set (pnmol_filter_set_reaction)";
-        return -1;
-    }
+    if (!has_term(f)) return refuse(f, who, "no reaction set (pnmol_filter_set_reaction)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (int rc = pnmol_reaction_enqueue(f, in->mean, in->frame_dt, dt)) return rc;
     f->sq_dt = -1.0;  // the operator changed: pnmol_filter_prepare_error_model comes next

@@ -38,3 +38,29 @@ def assert_mean_std_parity(means, stds, omeans, ostds):
     i.e. a std to ~2e-6*max(std) -- measured 2.2e-6 at N=256; the floor is 1e-5*max(std)."""
     np.testing.assert_allclose(means, omeans, rtol=1e-5, atol=1e-5 * np.abs(omeans).max())
     np.testing.assert_allclose(stds, ostds, rtol=1e-4, atol=1e-5 * np.abs(ostds).max())
+
+
+def assert_parity(means, stds, omeans, ostds, nu):
+    """North-star tolerances; at nu = 3 the two noise-free Dirichlet nodes get the 1e-3 max(std) allowance of the project's
+    nu = 3 tests (tests/test_gpu_smooth.py::test_smooth_heat_nu3; DESIGN.md section 6)."""
+    if nu < 3:
+        return assert_mean_std_parity(means, stds, omeans, ostds)
+    assert_mean_std_parity(means[:, 1:-1], stds[:, 1:-1], omeans[:, 1:-1], ostds[:, 1:-1])
+    np.testing.assert_allclose(means, omeans, rtol=1e-5, atol=1e-5 * np.abs(omeans).max())
+    np.testing.assert_allclose(stds[:, [0, -1]], ostds[:, [0, -1]], rtol=0, atol=1e-3 * ostds.max())
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+def per_step(solver, pde):
+    """Means, stds and diffusion_squared_local of `solve()`, step by step."""
+    means, stds, sig = [], [], []
+    for state, _ in solver.solution_generator(pde):
+        means.append(state.y.mean[0])
+        stds.append(np.sqrt(np.maximum(state.y.marginal_var[0], 0.0)))
+        if not isinstance(state.diffusion_squared_local, list):
+            sig.append(state.diffusion_squared_local)
+    return np.array(means), np.array(stds), np.array(sig)

@@ -10,26 +10,11 @@ import pytest
 
 import pnmol
 from convection_reference import CASES, DT, KAPPA, RATE, kw, oracle_solve, product
-from helpers import assert_mean_std_parity
+from helpers import assert_mean_std_parity, assert_parity as _assert_parity, per_step as _per_step, rel as _rel
 from pnmol import _hip
 from pnmol.pde import reactions
 
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _assert_parity(means, stds, omeans, ostds, nu):
-    """North-star tolerances; at nu = 3 the two noise-free Dirichlet nodes get the 1e-3 max(std) allowance of DESIGN.md section 6,
-    exactly as tests/test_gpu_reaction.py applies it."""
-    if nu < 3:
-        return assert_mean_std_parity(means, stds, omeans, ostds)
-    assert_mean_std_parity(means[:, 1:-1], stds[:, 1:-1], omeans[:, 1:-1], ostds[:, 1:-1])
-    np.testing.assert_allclose(means, omeans, rtol=1e-5, atol=1e-5 * np.abs(omeans).max())
-    np.testing.assert_allclose(stds[:, [0, -1]], ostds[:, [0, -1]], rtol=0, atol=1e-3 * ostds.max())
 
 
 # ------------------------------------------------------------------------------------------------------------ 1. stage parity
@@ -82,16 +67,6 @@ def test_linearize_route_equals_the_host_route_stage_by_stage(hip_ctx, variant, 
 # ------------------------------------------------------------------------------------------------------------ 2. loop against steps
 LOOP_CASES = [("burgers", 33, 2, "dirichlet", 24), ("burgers", 33, 2, "neumann", 8.3),     # runt last step: another dt
               ("burgers", 33, 3, "dirichlet", 12), ("burgers_fisher", 33, 2, "dirichlet", 9), ("burgers", 264, 2, "dirichlet", 3)]
-
-
-def _per_step(solver, pde):
-    means, stds, sig = [], [], []
-    for state, _ in solver.solution_generator(pde):
-        means.append(state.y.mean[0])
-        stds.append(np.sqrt(np.maximum(state.y.marginal_var[0], 0.0)))
-        if not isinstance(state.diffusion_squared_local, list):
-            sig.append(state.diffusion_squared_local)
-    return np.array(means), np.array(stds), np.array(sig)
 
 
 @pytest.mark.parametrize("variant,N,nu,bcond,K", LOOP_CASES)
@@ -241,6 +216,34 @@ def test_swapping_a_convection_for_a_reaction_and_back(hip_ctx):
         o, info, err = f.step(s, DT)
         outs.append((o.mean(), o.marginal_var(), info.diffusion_squared_local, err))
     assert all(np.array_equal(x, y) for x, y in zip(*outs))
+
+
+def test_a_system_and_a_convection_term_share_one_image_slot(hip_ctx):
+    """A filter owns one term image: system (built) -> convection (replaces it, wider) -> the same system (rebuilt) -> cleared
+    gives, segment by segment, the bits of a fresh filter that only ever held that term.  d = 34, nu = 2: Lotka-Volterra on the
+    two halves of the mesh adds one same-point column to every row (width 4), the 5-point gradient two (width 5)."""
+    N = 34
+    pde, conv_only = product("burgers", N, 2, "dirichlet", 24 * DT, gradient_stencil_size=5)
+    bare = [product("burgers", N, 2, "dirichlet", 24 * DT, gradient_stencil_size=5, reaction_on_device=False)[1] for _ in range(3)]
+    ref = conv_only.initialize(pde).y.device_state
+    mean0, cov0 = ref.mean(), ref.cov()
+    for s in bare:
+        s.initialize(pde)
+    fc, (fs, fsys, flin) = conv_only._device_filter, (s._device_filter for s in bare)
+    assert fc.reaction is pde.reaction and fs.reaction is fsys.reaction is flin.reaction is None and fs.d == N
+    system = reactions.lotka_volterra()
+    fsys.set_reaction(system)
+    want_sys, want_conv, want_lin = _loop(fsys, mean0, cov0), _loop(fc, mean0, cov0), _loop(flin, mean0, cov0)
+    assert not np.array_equal(want_sys[0], want_conv[0]) and not np.array_equal(want_sys[0], want_lin[0])
+    assert not np.array_equal(want_conv[0], want_lin[0])
+    fs.set_reaction(system)
+    assert _same(_loop(fs, mean0, cov0), want_sys)
+    fs.set_reaction(pde.reaction)
+    assert _same(_loop(fs, mean0, cov0), want_conv)
+    fs.set_reaction(system)
+    assert _same(_loop(fs, mean0, cov0), want_sys)
+    fs.set_reaction(None)
+    assert _same(_loop(fs, mean0, cov0), want_lin)
 
 
 # ------------------------------------------------------------------------------------------------------------ 7. refusals

@@ -10,7 +10,7 @@ import pytest
 
 import pnmol
 import pnmol_oracle as oracle
-from helpers import assert_mean_std_parity
+from helpers import assert_mean_std_parity, assert_parity as _assert_parity, per_step as _per_step, rel as _rel
 from pnmol import _hip
 from pnmol.pde import reactions
 from smooth_reference import marginal_std, rts_on_oracle
@@ -60,21 +60,6 @@ def _oracle(name, N, nu, bcond, tmax, adaptive=None):
         osol = osolver.solve(opde)
         _ORACLE[key] = (osolver, osol) + tuple(oracle.read_mean_and_std(osol, osolver.E0))
     return _ORACLE[key]
-
-
-def _assert_parity(means, stds, omeans, ostds, nu):
-    """North-star tolerances; at nu = 3 the two noise-free Dirichlet nodes get the 1e-3 max(std) allowance of the project's
-    nu = 3 tests (tests/test_gpu_smooth.py::test_smooth_heat_nu3; DESIGN.md section 6)."""
-    if nu < 3:
-        return assert_mean_std_parity(means, stds, omeans, ostds)
-    assert_mean_std_parity(means[:, 1:-1], stds[:, 1:-1], omeans[:, 1:-1], ostds[:, 1:-1])
-    np.testing.assert_allclose(means, omeans, rtol=1e-5, atol=1e-5 * np.abs(omeans).max())
-    np.testing.assert_allclose(stds[:, [0, -1]], ostds[:, [0, -1]], rtol=0, atol=1e-3 * ostds.max())
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 # ------------------------------------------------------------------------------------------------------------ 1. stage parity
@@ -150,16 +135,6 @@ MARGINAL_CASES = SOLVE_CASES + [
     ("logistic", 32, 2, "dirichlet", 25),     # odd number of steps: the result lives in the filter's spare buffers
     ("logistic", 32, 2, "dirichlet", 8.3),    # runt last step: another dt, a frame change inside k_linearize
 ]
-
-
-def _per_step(solver, pde):
-    means, stds, sig = [], [], []
-    for state, _ in solver.solution_generator(pde):
-        means.append(state.y.mean[0])
-        stds.append(np.sqrt(np.maximum(state.y.marginal_var[0], 0.0)))
-        if not isinstance(state.diffusion_squared_local, list):
-            sig.append(state.diffusion_squared_local)
-    return np.array(means), np.array(stds), np.array(sig)
 
 
 @pytest.mark.parametrize("name,N,nu,bcond,K", MARGINAL_CASES)

@@ -10,7 +10,7 @@ import pytest
 
 import pnmol
 import pnmol_oracle as oracle
-from helpers import assert_mean_std_parity
+from helpers import assert_mean_std_parity, assert_parity, per_step as _per_step, rel as _rel
 from pnmol import _hip
 from pnmol.pde import examples, reactions
 from smooth_reference import marginal_std, rts_on_oracle
@@ -65,19 +65,9 @@ def _components(C, *arrays):
 
 def _assert_parity(C, means, stds, omeans, ostds, nu):
     """North-star tolerances per component; at nu = 3 the boundary nodes of every component get the 1e-3 max(std) allowance of
-    the project's nu = 3 tests (tests/test_gpu_reaction.py, `_assert_parity`)."""
+    the project's nu = 3 tests (tests/helpers.py, `assert_parity`)."""
     for m, s, om, os_ in _components(C, means, stds, omeans, ostds):
-        if nu < 3:
-            assert_mean_std_parity(m, s, om, os_)
-            continue
-        assert_mean_std_parity(m[:, 1:-1], s[:, 1:-1], om[:, 1:-1], os_[:, 1:-1])
-        np.testing.assert_allclose(m, om, rtol=1e-5, atol=1e-5 * np.abs(om).max())
-        np.testing.assert_allclose(s[:, [0, -1]], os_[:, [0, -1]], rtol=0, atol=1e-3 * os_.max())
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / np.abs(b).max())
+        assert_parity(m, s, om, os_, nu)
 
 
 def _scatter(blocks):
@@ -175,16 +165,6 @@ MARGINAL_CASES = [
     ("lotka_volterra", 24, 2, 8.3, True),     # runt last step: another dt, a frame change inside k_linearize_system
     ("lotka_volterra", 24, 3, 12, False),     # n = 4, the other sweep kernel: against solve() only
 ]
-
-
-def _per_step(solver, pde):
-    means, stds, sig = [], [], []
-    for state, _ in solver.solution_generator(pde):
-        means.append(state.y.mean[0])
-        stds.append(np.sqrt(np.maximum(state.y.marginal_var[0], 0.0)))
-        if not isinstance(state.diffusion_squared_local, list):
-            sig.append(state.diffusion_squared_local)
-    return np.array(means), np.array(stds), np.array(sig)
 
 
 @pytest.mark.parametrize("name,N,nu,K,with_oracle", MARGINAL_CASES)
