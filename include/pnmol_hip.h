@@ -292,6 +292,43 @@ typedef struct pnmol_observe_out {
 int pnmol_state_observe(pnmol_filter* f, const pnmol_state* in, int q, const double* C_q_ds, const double* y_q,
                         const double* R_sqrtm_qq, pnmol_state* out, pnmol_observe_out* res);
 
+/* Sensor data in the constant-step loop ------------------------------------------------------------------------------------------
+ * A fixed sensor array -- C (q, d_state) and R_sqrtm (q, q) shared by all times -- that reports y_i at the times t_i: the plan of a
+ * filter.  With a plan set, `pnmol_filter_steps_begin(f, s, k, dt)` walks the times the call reaches (t = s->t; t += dt per step) and
+ * enqueues the update of the pending entry whose time agrees with the time behind step j (16 ulp, as everywhere) right behind that
+ * step, in place on the state; later steps start from the conditioned state.  No host round trip in between and one synchronisation
+ * per call, as without data.  The update is `pnmol_state_observe`'s (same model, same formulas) with y, C and R read from the plan's
+ * device tables and the three scalars kept on the device until the call's copy-out: the kernels of `pnmol_state_observe` in their
+ * order, bit for bit its result.  With PNMOL_HIP_OBSERVE_SINGLE_WG=1 in the environment when the plan is set, a plan of q <= 32 takes
+ * a route without the sweep launch instead (one workgroup factorises S in LDS; rounding-level differences).  It measured 0.03 ms
+ * slower per update than the sweep route and is therefore not the default; the switch keeps it measurable.
+ * `_begin` returns -1 before anything is enqueued, `s` untouched, `pnmol_last_error` naming entry and time, when the next pending entry
+ * lies before s->t, at s->t (it was never applied: apply it with `pnmol_state_observe_planned` or `pnmol_state_observe` first) or
+ * strictly between two grid times of the call.  Entries behind s->t + k dt stay pending for the next call.
+ * `_end` fills the results and advances the cursor; row j of means_kd / stds_kd is that of the conditioned state when an entry was
+ * applied behind step j; info_k[j] keeps its meaning (the PDE residual only).  -3 when an update's innovation matrix is not positive
+ * definite (entry and pivot in `pnmol_last_error`; a dropped pivot is an error here); a step's own error at or before that step
+ * takes precedence.  While entries are pending the loop runs its self-contained steps (as with a nonlinear term); a filter without a
+ * plan, or whose plan is cleared, takes the launches and gives the bits it always did.  A term set by `pnmol_filter_set_reaction` /
+ * `_system` / `_convection` composes with a plan.  `pnmol_filter_destroy` frees the plan.
+ *
+ * `pnmol_filter_set_observations`: nobs = 0 or t_nobs = NULL clears.  Copies everything (t_nobs (nobs), C_q_ds (q, d_state) row-major,
+ * R_sqrtm_qq (q, q) lower triangular or NULL: noise-free, y_nobs_q (nobs, q) row-major); resets the cursor to entry 0.  -1 (reason in
+ * `pnmol_last_error`): null filter, fp32 filter, q < 1, q > d_state, times not strictly increasing or not finite, a non-finite entry
+ * of C, R or y, R not lower triangular, an unfinished `pnmol_filter_steps_begin`.  -4: out of memory.  Synchronises the stream.
+ * `pnmol_filter_observations_pending`: the cursor (index of the first entry not applied) and the number of entries (0, 0: no plan).
+ * `pnmol_filter_observation_results`: results of the entries [first, first + count), which must have been applied (-1 otherwise).
+ * `pnmol_state_observe_planned`: entry `index` applied to `s` IN PLACE, now, by exactly the path the loop takes (enqueue, then one
+ * synchronisation), in the frame `s` is in; the time of the entry is not compared with s->t.  Does not move the cursor unless
+ * index == next, in which case it advances it.  -1: null, foreign state, no plan, index outside the plan, an unfinished
+ * `pnmol_filter_steps_begin`; -3 as for `pnmol_state_observe`. */
+int pnmol_filter_set_observations(pnmol_filter* f, int nobs, const double* t_nobs, int q, const double* C_q_ds,
+                                  const double* R_sqrtm_qq /* lower triangular; NULL: noise-free */,
+                                  const double* y_nobs_q);
+int pnmol_filter_observations_pending(const pnmol_filter* f, int* next, int* nobs);
+int pnmol_filter_observation_results(const pnmol_filter* f, int first, int count, pnmol_observe_out* res);
+int pnmol_state_observe_planned(pnmol_filter* f, pnmol_state* s, int index, pnmol_observe_out* res);
+
 /* Dense output: the posterior BETWEEN grid times ------------------------------------------------------------------------------
  * Between two grid times there is no measurement, so given the states at the two ends of a step the state at t inside it follows
  * the bridge of the prior IWP (x) K, under the prior and under every posterior alike.  With h = dt, theta = (t - t_k) / h in (0, 1),

@@ -3457,9 +3457,11 @@ void drop_graphs(pnmol_filter* f);
 enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 
 // The loop is not fused while a reaction is set: the fused loop makes the next step's z and G inside the previous step's
-// k_readout launch, before that step's re-linearisation could run.
+// k_readout launch, before that step's re-linearisation could run.  The same holds while a sensor plan has pending entries
+// (pnmol_filter_set_observations): z and G of the step behind an update would come from the unconditioned state, and the fused
+// steps write P only in the call's last step, while the update conditions P itself.
 inline bool fused_loop(const pnmol_filter* f) {
-    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f);
+    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f) && !pnmol_observe_plan_pending(f);
 }
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
@@ -3729,7 +3731,9 @@ int prepare_graphs(pnmol_filter* f, pnmol_state* s, int k, double dt, hipGraphEx
     double *gP0 = lead ? nxtP : curP, *gM0 = lead ? nxtM : curM, *gP1 = lead ? curP : nxtP, *gM1 = lead ? curM : nxtM;
     int rc = 0;
     if (rest >= f->graph_chunk) rc = get_graph(f, gP0, gM0, gP1, gM1, s->var, dt, f->graph_chunk, gbig);
-    if (rc == 0 && (rest % f->graph_chunk) >= 2) rc = get_graph(f, gP0, gM0, gP1, gM1, s->var, dt, 2, gpair);
+    // (a pending sensor plan cuts the call into runs between updates: they take the pair graph whatever k is)
+    if (rc == 0 && ((rest % f->graph_chunk) >= 2 || (pnmol_observe_plan_pending(f) && rest >= 2)))
+        rc = get_graph(f, gP0, gM0, gP1, gM1, s->var, dt, 2, gpair);
     return rc;
 }
 
@@ -3753,7 +3757,9 @@ __global__ __launch_bounds__(256) void k_cov_reference_order(const void* __restr
 // of four hipMemcpyAsync calls (no SDMA queue, no runtime copy path inside the step loop).
 __global__ __launch_bounds__(256) void k_copy_out(const double* __restrict__ rec, const double* __restrict__ means,
                                                   const double* __restrict__ stds, const int* __restrict__ info,
-                                                  double* __restrict__ out, int k, int d, int cap) {
+                                                  double* __restrict__ out, int k, int d, int cap,
+                                                  const double* __restrict__ ob_res, double* __restrict__ ob_out, int ob_first,
+                                                  int ob_count) {
     const long nm = (long)k * d;
     double* hm = out + (size_t)4 * cap;
     double* hs = hm + (size_t)cap * d;
@@ -3765,6 +3771,8 @@ __global__ __launch_bounds__(256) void k_copy_out(const double* __restrict__ rec
     if (blockIdx.x == 0) {
         for (int e = threadIdx.x; e < 4 * k; e += 256) out[e] = rec[e];
         for (int e = threadIdx.x; e < k; e += 256) hi[e] = info[e];
+        // (a sensor plan: the result slots of the entries this call applied)
+        for (int e = threadIdx.x; e < 4 * ob_count; e += 256) ob_out[4 * ob_first + e] = ob_res[4 * ob_first + e];
     }
 }
 
@@ -4309,6 +4317,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_sample_free_ws(f);
     pnmol_dense_free_ws(f);
     pnmol_observe_free_ws(f);
+    pnmol_observe_plan_free(f);
     pnmol_reaction_free_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
@@ -4741,7 +4750,7 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
     k_init_call<<<1, 64, 0, ctx->stream>>>(f->info, 1, f->ctr, f->last_ctr);
     int rc = dispatch_step(f, in->P, in->mean, in->frame_dt, dt, out->P, out->mean, out->var, false);
     if (rc != 0) return rc;
-    k_copy_out<<<1, 256, 0, ctx->stream>>>(f->rec, nullptr, nullptr, f->info, f->h_pin_dev, 1, f->d, f->rec_cap);
+    k_copy_out<<<1, 256, 0, ctx->stream>>>(f->rec, nullptr, nullptr, f->info, f->h_pin_dev, 1, f->d, f->rec_cap, nullptr, nullptr, 0, 0);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     double rec[4];
     std::memcpy(rec, f->h_pin, sizeof(rec));
@@ -4775,7 +4784,17 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     }
     pnmol_ctx* ctx = f->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_rec(f, k);
+    // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
+    std::vector<int> ob_entry;
+    int rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
+    if (rc != 0) return rc;
+    const bool planned = pnmol_observe_plan_pending(f);
+    struct PlanGuard {  // a call that fails before it is enqueued in full leaves no bookkeeping behind
+        pnmol_filter* f;
+        bool armed = true;
+        ~PlanGuard() { if (armed) pnmol_observe_plan_abandon(f); }
+    } plan_guard{f};
+    rc = ensure_rec(f, k);
     if (rc != 0) return rc;
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
@@ -4791,20 +4810,35 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     if (rc != 0) return rc;
     const double tB = now();
     HIPCHK(ctx, hipEventRecord(f->ev0, st));
+    // the buffer a captured graph starts from (prepare_graphs): with a plan the eager steps around the updates move the parity
+    double* const graphP0 = (s->frame_dt != dt || fused) ? f->tmpP : s->P;
+    // the update of the plan entry mapped behind step j (if any), in place on the buffers that hold the state there
+    const auto update_behind = [&](int j) {
+        if (!planned || ob_entry[(size_t)j] < 0) return 0;
+        return pnmol_observe_plan_enqueue(f, ob_entry[(size_t)j], curP, curM, s->var, dt, j);
+    };
     int it = 0;
     while (it < k) {
-        const int left = k - it;
-        const bool may_graph = frame == dt && (it > 0 || !fused);  // fused loop: step 0 does the full predict (eager)
+        int left = k - it;
+        bool may_graph = frame == dt && (it > 0 || !fused);  // fused loop: step 0 does the full predict (eager)
+        if (planned) {  // a graph may end on a step with an update behind it, not run across one
+            int run = 1;
+            while (it + run - 1 < k - 1 && ob_entry[(size_t)(it + run - 1)] < 0 && run < left) ++run;
+            left = run;
+            may_graph = may_graph && curP == graphP0;
+        }
         if (may_graph && gbig && left >= f->graph_chunk) {
             HIPCHK(ctx, hipGraphLaunch(gbig, st));
             for (auto& g : f->graphs) g.launched = g.launched || g.exec == gbig;
             it += f->graph_chunk;  // even number of steps: buffers are back where they started
+            if ((rc = update_behind(it - 1)) != 0) return rc;
             continue;
         }
         if (may_graph && gpair && left >= 2) {
             HIPCHK(ctx, hipGraphLaunch(gpair, st));
             for (auto& g : f->graphs) g.launched = g.launched || g.exec == gpair;
             it += 2;
+            if ((rc = update_behind(it - 1)) != 0) return rc;
             continue;
         }
         rc = loop_step(f, curP, curM, frame, dt, nxtP, nxtM, s->var, !fused ? STEP_FULL : (it == 0 ? STEP_FIRST : STEP_STEADY));
@@ -4814,6 +4848,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
         t = curM, curM = nxtM, nxtM = t;
         frame = dt;
         ++it;
+        if ((rc = update_behind(it - 1)) != 0) return rc;
     }
     HIPCHK(ctx, hipEventRecord(f->ev1, st));
     const double tC = now();
@@ -4823,7 +4858,14 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
         s->P = curP, s->mean = curM;
     }
     // device -> pinned staging (allocated in ensure_rec); handed to the caller by pnmol_filter_steps_end
-    k_copy_out<<<64, 256, 0, st>>>(f->rec, f->rec_means, f->rec_stds, f->info, f->h_pin_dev, k, f->d, f->rec_cap);
+    {
+        double* ob_out = nullptr;
+        int ob_first = 0, ob_count = 0;
+        const double* ob_res = pnmol_observe_plan_results_dev(f, &ob_out, &ob_first, &ob_count);
+        k_copy_out<<<64, 256, 0, st>>>(f->rec, f->rec_means, f->rec_stds, f->info, f->h_pin_dev, k, f->d, f->rec_cap, ob_res, ob_out,
+                                       ob_first, ob_count);
+    }
+    plan_guard.armed = false;
     if (trace)
         std::fprintf(stderr, "[pnmol] steps_begin(k=%d): prepare %.2f ms, enqueue %.2f ms, graphs big=%d pair=%d\n", k, tB - tA,
                      tC - tB, gbig != nullptr, gpair != nullptr);
@@ -4864,6 +4906,14 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
     }
     s->t = t;
     s->frame_dt = dt;
+    // a sensor plan: the results of the entries this call applied; the cursor moves.  The update behind step j comes after step j
+    // in time, so a step's own error at or before j takes precedence.
+    int ob_step = -1;
+    const int ob_rc = pnmol_observe_plan_collect(f, &ob_step);
+    if (ob_rc != 0) {
+        const int first = stuck >= 0 && (bad < 0 || stuck < bad) ? stuck : bad;  // the first step that failed by itself
+        if (first < 0 || first > ob_step) return ob_rc;                         // (ctx->err names entry, pivot and step)
+    }
     if (stuck >= 0) {
         ctx->err = "sweep kernel: a dependency wait timed out in step " + std::to_string(stuck);
         return -2;
@@ -4899,7 +4949,9 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
     if (e == hipSuccess) e = hipMemcpyAsync(bak + nP, s->mean, sizeof(double) * Dp, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(bak + nP + Dp, s->var, sizeof(double) * Dp, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) {
+        const int ob_next = pnmol_observe_plan_cursor(f);  // (a sensor plan: the rehearsal applies entries; the cursor goes back)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
+        pnmol_observe_plan_rewind(f, ob_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pnmol_hip.h"
+#include "pnmol_observe_plan.hpp"  // (times_agree lives there: the plan's walk uses it without anything of HIP)
 
 constexpr int NB = 32;    // factorisation block
 constexpr int MAXN = 4;   // max derivatives + 1
@@ -184,6 +185,8 @@ struct pnmol_filter {
     struct BridgeSlab* dn_slab = nullptr;  // the slab new bridges take their block from
     // Measurement updates (pnmol_state_observe): one workspace per padded column count, allocated on first use
     std::vector<ObserveWs*> ob_ws;
+    // Sensor data in the constant-step loop (pnmol_filter_set_observations, pnmol_observe.hip): NULL = no plan
+    struct ObservePlanDev* ob_plan = nullptr;
     // The nonlinear term the device linearises itself (pnmol_reaction.hip): none, a pointwise reaction (pnmol_filter_set_reaction),
     // a coupled system (pnmol_filter_set_reaction_system) or a convection term (pnmol_filter_set_convection), with the descriptor of
     // that kind.  While one is set the constant-step loop re-linearises in front of every step, runs non-fused and carries no error
@@ -248,10 +251,6 @@ inline void frame_scales(const pnmol_state* s, double* sc) { frame_scales(s->f, 
 inline double frame_ratio(const pnmol_filter* f, int a, double from_dt, double to_dt) {
     return (from_dt == 0.0 ? 1.0 : nordsieck_scale(f->nu, a, from_dt)) / nordsieck_scale(f->nu, a, to_dt);
 }
-// two times are the same grid point (dt: the step they are measured against)
-inline bool times_agree(double a, double b, double dt) {
-    return std::fabs(a - b) <= 16.0 * 2.220446049250313e-16 * std::max({std::fabs(a), std::fabs(b), std::fabs(dt)});
-}
 // lower Cholesky factor of the leading n x n block of A (row pitch MAXN; L zero on entry).  semidefinite: a pivot that is
 // not positive gives a zero column instead of a NaN.
 inline void small_cholesky(int n, const double* A, double* L, bool semidefinite = false) {
@@ -272,6 +271,28 @@ void pnmol_dense_free_ws(pnmol_filter* f);
 void pnmol_observe_free_ws(pnmol_filter* f);
 // pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
+
+// pnmol_observe.hip: the sensor plan inside pnmol_filter_steps_begin / _end.  pending: a plan with entries that have not been applied
+// is set (the loop then runs non-fused: the fused loop prepares the next step's z and G from the unconditioned state).
+bool pnmol_observe_plan_pending(const pnmol_filter* f);
+// the walk of a call of k steps of dt from s (refusals: -1, ctx->err set, nothing enqueued); entry_of_step[j] >= 0: an update
+// goes behind step j.  Without a pending plan: all -1.
+int pnmol_observe_plan_begin(pnmol_filter* f, const pnmol_state* s, int k, double dt, std::vector<int>* entry_of_step);
+// enqueue the update of `entry` on the state (P, mean, var in the frame frame_dt), in place, on the ctx stream; rec_slot >= 0: the
+// step record of that slot is overwritten from the conditioned state.  No synchronisation.
+int pnmol_observe_plan_enqueue(pnmol_filter* f, int entry, double* P, double* mean, double* var, double frame_dt, int rec_slot);
+// behind the call's synchronisation: results of the call's entries from the staging buffer, the cursor moves.  0, or -2 / -3 with
+// *step = the step whose update failed (ctx->err names entry and pivot)
+int pnmol_observe_plan_collect(pnmol_filter* f, int* step);
+// the device result slots the running call fills and where they go (mapped staging): the loop's copy-out kernel carries them home.
+// NULL: the call applies no entry.
+const double* pnmol_observe_plan_results_dev(const pnmol_filter* f, double** host_dev, int* first, int* count);
+// drop the bookkeeping of a call that was refused or failed before it was enqueued in full
+void pnmol_observe_plan_abandon(pnmol_filter* f);
+// the cursor, and putting it back (pnmol_filter_prepare_steps rehearses a call): entries from `next` on count as not applied again
+int pnmol_observe_plan_cursor(const pnmol_filter* f);
+void pnmol_observe_plan_rewind(pnmol_filter* f, int next);
+void pnmol_observe_plan_free(pnmol_filter* f);
 
 void pnmol_reaction_free_ws(pnmol_filter* f);
 // pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system, k_linearize_convection for a convection

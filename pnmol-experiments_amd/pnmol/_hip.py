@@ -93,6 +93,11 @@ SYMBOLS = {
     "pnmol_state_predict": (ctypes.c_int, [_vp, _vp, ctypes.c_double, _vp]),
     "pnmol_state_observe": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _vp,
                                            ctypes.POINTER(ObserveOut)]),
+    "pnmol_filter_set_observations": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p,
+                                                     _c_double_p]),
+    "pnmol_filter_observations_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_filter_observation_results": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ObserveOut)]),
+    "pnmol_state_observe_planned": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(ObserveOut)]),
     "pnmol_state_predict_marginals": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p]),
     "pnmol_smoother_step_bridge": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
     "pnmol_bridge_destroy": (ctypes.c_int, [_vp]),
@@ -455,6 +460,51 @@ class Filter:
                                           out.handle, ctypes.byref(res))
         self.ctx.check(rc, "pnmol_state_observe")
         return out, res
+
+    def set_observations(self, times, C, ys, R_sqrtm=None):
+        """The sensor plan of the constant-step loop (`pnmol_filter_set_observations`): a fixed sensor array C (q, d_state),
+        R_sqrtm (q, q) lower triangular or None (noise-free), reporting ys[i] (nobs, q) at times[i].  `steps` then conditions the
+        state behind the step that lands on each time, on the device; the cursor starts at entry 0."""
+        t = _f64(np.atleast_1d(times))
+        C = _f64(C)
+        if t.ndim != 1 or t.size < 1:
+            raise ValueError(f"times must be a non-empty 1-d array, got shape {t.shape}")
+        if C.ndim != 2 or C.shape[1] != self.ds or not 1 <= C.shape[0] <= self.ds:
+            raise ValueError(f"C must be (q, {self.ds}) with 1 <= q <= {self.ds}, got {C.shape}")
+        q = C.shape[0]
+        ys = _f64(ys, (t.size, q))
+        R = None if R_sqrtm is None else _f64(R_sqrtm, (q, q))
+        rc = self.lib.pnmol_filter_set_observations(self.handle, t.size, _dp(t), q, _dp(C), None if R is None else _dp(R), _dp(ys))
+        self.ctx.check(rc, "pnmol_filter_set_observations")
+
+    def clear_observations(self):
+        """Drop the sensor plan: the filter then takes the launches and gives the bits of one that never had a plan."""
+        self.ctx.check(self.lib.pnmol_filter_set_observations(self.handle, 0, None, 0, None, None, None),
+                       "pnmol_filter_set_observations")
+
+    def observations_pending(self):
+        """(next, nobs): the plan's cursor -- the first entry that has not been applied -- and its length ((0, 0): no plan)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.pnmol_filter_observations_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
+                       "pnmol_filter_observations_pending")
+        return nxt.value, n.value
+
+    def observation_results(self, first=0, count=None):
+        """ObserveOut of the applied plan entries [first, first + count) (default: up to the cursor)."""
+        if count is None:
+            count = self.observations_pending()[0] - first
+        res = (ObserveOut * max(count, 1))()
+        self.ctx.check(self.lib.pnmol_filter_observation_results(self.handle, int(first), int(count), res),
+                       "pnmol_filter_observation_results")
+        return list(res)[:count]
+
+    def observe_planned(self, state, index):
+        """Entry `index` of the plan applied to `state` IN PLACE, by the path the loop takes (`pnmol_state_observe_planned`):
+        ObserveOut."""
+        res = ObserveOut()
+        rc = self.lib.pnmol_state_observe_planned(self.handle, state.handle, int(index), ctypes.byref(res))
+        self.ctx.check(rc, "pnmol_state_observe_planned")
+        return res
 
     def predict(self, state, dt):
         """The prior alone carried over dt > 0 from `state` (`pnmol_state_predict`): a new State at state.t + dt."""

@@ -119,6 +119,23 @@ def prepare(observations, pde, steprule, d):
     return obs
 
 
+def shared_sensors(observations):
+    """(times, C, R_sqrtm, ys) of observations that share one sensor array: what the device-resident loop takes
+    (`solve_marginals(pde, observations=...)`, `pnmol_filter_set_observations`).  ys is (nobs, q); R_sqrtm is None when noise-free."""
+    obs = list(observations)
+    if not obs:
+        raise ValueError("shared_sensors: no observations")
+    first = obs[0]
+    for i, o in enumerate(obs[1:], start=1):
+        same_noise = (o.R_sqrtm is None) == (first.R_sqrtm is None) and (o.R_sqrtm is None or (
+            o.R_sqrtm.shape == first.R_sqrtm.shape and np.array_equal(o.R_sqrtm, first.R_sqrtm)))
+        if o.C.shape != first.C.shape or not np.array_equal(o.C, first.C) or not same_noise:
+            what = "C" if o.C.shape != first.C.shape or not np.array_equal(o.C, first.C) else "noise factor"
+            raise ValueError(f"observation {i} (t={o.t}) has another {what} than observation 0: the device-resident loop takes one "
+                             f"sensor array for all times; use solve(pde, observations=...) for per-time sensors")
+    return (np.array([o.t for o in obs]), first.C, first.R_sqrtm, np.stack([o.y for o in obs]))
+
+
 def merged_stops(stop_at, obs, t0):
     """`stop_at` with the observation times behind t0 merged in, sorted; a stop that agrees with an observation time
     (`times_agree`) gives way to it, so that no step of a rounding error's length is taken between the two."""

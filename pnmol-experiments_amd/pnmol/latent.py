@@ -156,5 +156,5 @@ class SemiLinearLatentForceEK1(_LatentForceEK1Base):
     semilinear = True
     _linearize = staticmethod(white.SemiLinearWhiteNoiseEK1._linearize)
 
-    def solve_marginals(self, pde, *, num_steps=None):
+    def solve_marginals(self, pde, *, num_steps=None, observations=None):
         raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")

@@ -101,8 +101,11 @@ class _SqrtFormMixin:
     def _wants_error(self):
         return not isinstance(self.steprule, _step.Constant)   # Constant discards it (odetools/step.py:49-52)
 
-    def solve_marginals(self, pde, *, num_steps=None):
-        """As `pnmol.white.LinearWhiteNoiseEK1.solve_marginals`, the loop kept on the device in square-root form."""
+    def solve_marginals(self, pde, *, num_steps=None, observations=None):
+        """As `pnmol.white.LinearWhiteNoiseEK1.solve_marginals`, the loop kept on the device in square-root form (which takes no
+        observations: `_check_observations_supported`)."""
+        if observations is not None:
+            self._check_observations_supported()
         if self.semilinear:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
         state = self.initialize(pde)

@@ -296,19 +296,29 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         ref = None if state.reference_state is None else np.abs(m_new[0][:observation.C.shape[1]])
         return state._replace(y=rv.DeviceMultivariateNormal(m_new, dev_out), reference_state=ref), res.log_likelihood
 
-    def solve_marginals(self, pde, *, num_steps=None):
+    def solve_marginals(self, pde, *, num_steps=None, observations=None):
         """Constant-step solve that keeps everything on the device: returns
         (t (T+1,), means (T+1,d), stds (T+1,d), diffusion_squared_local (T,), final PDEFilterState).
 
         `means`/`stds` are `sol.mean[:, 0]` and sqrt(diag(cov) E0^T) of the reference's read-out
         (experiments/figure1.py:76-80).  Steps follow the t-accumulation of the reference's loop
         (pdefilter.py:140-160, :220-223), including a runt final step when sum(dt) lands short of tmax.
+
+        observations (beyond the reference): `pnmol.data.Observation`s of ONE sensor array (`pnmol.data.shared_sensors`) at grid
+        times; the state is conditioned on each behind the step that lands on its time, inside the device loop
+        (`pnmol_filter_set_observations`), and the rows of `means` / `stds` are those of the conditioned
+        states.  The result then has a sixth element `info = dict(num_steps, data_log_likelihood, data_log_likelihoods)`, as
+        `solve(pde, observations=...)` reports them.  Per-time sensor arrays stay with `solve()`.
         """
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_marginals needs the Constant step rule")
-        state = self.initialize(pde)
-        dev = state.y.device_state
-        on_device = self._device_filter.reaction is not None    # re-linearised inside the loop; no error model there
+        if observations is not None:
+            return self._solve_marginals_observed(pde, num_steps, observations)
+        ts, dts = self._constant_schedule(pde, num_steps)
+        return self._run_device_loop(pde, self.initialize(pde), ts, dts)
+
+    def _constant_schedule(self, pde, num_steps):
+        """(times, steps) of the constant-step loop: the t-accumulation of the reference, a runt final step included."""
         dt0 = self.steprule.first_dt(pde)
         ts, dts, t, dt = [pde.t0], [], pde.t0, dt0
         while t < pde.tmax and (num_steps is None or len(dts) < num_steps):
@@ -316,6 +326,12 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             t = t + dt
             ts.append(t)
             dt = min(dt0, pde.tmax - t)
+        return ts, dts
+
+    def _run_device_loop(self, pde, state, ts, dts):
+        """The steps `dts` from `state` on the device, runs of equal dt in one call each: the 5-tuple of `solve_marginals`."""
+        dev = state.y.device_state
+        on_device = self._device_filter.reaction is not None    # re-linearised inside the loop; no error model there
         d = pde.L.shape[0]                                      # (the latent-force state carries eps behind u)
         means = [state.y.mean[0][:d]]
         stds = [np.sqrt(np.maximum(state.y.marginal_var[0][:d], 0.0))]
@@ -336,6 +352,44 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                                          reference_state=np.abs(m_final[0][:d]),
                                          diffusion_squared_local=sig[-1] if sig else [])
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
+
+    def _solve_marginals_observed(self, pde, num_steps, observations):
+        """`solve_marginals` with sensor data: everything is validated on the host before `initialize` binds the device."""
+        from . import data
+
+        self._check_observations_supported()
+        obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
+        dt0 = self.steprule.first_dt(pde)
+        ts, dts = self._constant_schedule(pde, num_steps)
+        if obs:
+            times, C, R, ys = data.shared_sensors(obs)
+            if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
+                raise ValueError(f"observation at t={times[-1]} lies behind the last step taken (t={ts[-1]}, {len(dts)} steps)")
+        state = self.initialize(pde)
+        flt = self._device_filter
+        lls = []
+        if obs and data.times_agree(obs[0].t, pde.t0, dt0):     # at t0: the initial state, as solve() does it
+            state, ll = self._observe(state, obs[0])
+            lls.append(ll)
+            times, ys = times[1:], ys[1:]
+        try:
+            if obs and times.size:
+                Cd = C if C.shape[1] == flt.ds else np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
+                flt.set_observations(times, Cd, ys, R)
+            out = self._run_device_loop(pde, state, ts, dts)
+            applied, nobs = flt.observations_pending()
+            if applied != nobs:
+                raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
+            lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
+        except BaseException:
+            try:                                                # (the failure above is the one to report, not one of the clear)
+                flt.clear_observations()
+            except _hip.PnmolHipError:
+                pass
+            raise
+        flt.clear_observations()
+        info = dict(num_steps=len(dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
+        return out + (info,)
 
     # ------------------------------------------------------------------ backward walks (smoothing, joint draws)
     def _walk_inputs(self, who, solution):
@@ -529,7 +583,7 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return None
         return reaction
 
-    def solve_marginals(self, pde, *, num_steps=None):
+    def solve_marginals(self, pde, *, num_steps=None, observations=None):
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
-        return super().solve_marginals(pde, num_steps=num_steps)
+        return super().solve_marginals(pde, num_steps=num_steps, observations=observations)
