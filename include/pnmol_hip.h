@@ -28,7 +28,8 @@
  *     `pnmol_smoother_step` and the joint draws (`pnmol_samples_*`, `pnmol_sample_noise`) were added within version 3:
  *     backwards-compatible additions, nothing existing changed.  So was the dense output (`pnmol_state_predict*`,
  *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`) and the measurement
- *     update (`pnmol_state_observe`).
+ *     update (`pnmol_state_observe`), the recorder of the constant-step loop (`pnmol_filter_set_recorder`, `_recorder_pending`,
+ *     `_recorder_means`) and the one-call backward pass (`pnmol_smoother_steps`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -221,7 +222,7 @@ int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, c
 
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);
-int pnmol_state_destroy(pnmol_state* s); /* -1 for the target of an unfinished pnmol_filter_steps_begin */
+int pnmol_state_destroy(pnmol_state* s); /* -1 for the target of an unfinished pnmol_filter_steps_begin, and for a slot of a set recorder */
 int pnmol_state_clone(const pnmol_state* s, pnmol_state** out); /* reject/retry, pdefilter.py:192-223 */
 /* upload `PDEFilterState(t, y=(mean, cov))`; cov = cov_sqrtm @ cov_sqrtm.T (base/rv.py:12-14) */
 int pnmol_state_set(pnmol_state* s, double t, const double* mean_nd, const double* cov_DD);
@@ -457,6 +458,55 @@ int pnmol_filter_steps(pnmol_filter* f, pnmol_state* s, int k, double dt, double
 int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt);
 int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, double* stds_kd,
                            pnmol_step_out* info_k);
+
+/* The filtered trajectory out of the constant-step loop -------------------------------------------------------------------------
+ * `PDEFilter.solve` of the reference stacks the state behind every step (pdefilter.py:140-160); through this ABI that used to take
+ * one `pnmol_filter_step` call, one synchronisation, one state and one mean read-back per step.  A recorder makes the loop above do
+ * it: `pnmol_filter_set_recorder(f, count, slots)` names caller-owned states of f, and slots[i] receives the state behind the i-th
+ * step taken from then on -- mean, full covariance and marginal variances in the frame of dt, copied on the device behind the
+ * step's read-out (one launch of k_record per step, the slot index taken from device words, so the captured graphs of the loop
+ * replay as before; no host round trip).  Steps are counted across successive `pnmol_filter_steps(_begin)` calls by a cursor, like
+ * the sensor plan's.  A step with a planned sensor update behind it records the conditioned state.  `_end` gives the call's slots
+ * their time and frame and moves the cursor; after a -2 / -3 the cursor has moved past the call and the slots from the failing step
+ * on are undefined (the sensor plan's rule).
+ * count = 0 or slots = NULL clears.  The call copies the list, uploads the device table of the slots' buffers and drops the captured
+ * graphs (the launch sequence differs with a recorder).  -1, nothing changed, reason in `pnmol_last_error`: a null slot, a slot of
+ * another filter, a slot listed twice, an fp32 filter, a call between `pnmol_filter_steps_begin` and `_end`.  -4: out of memory.
+ * With a recorder set
+ *   - `pnmol_filter_steps_begin(f, s, k, dt)` returns -1 before anything is enqueued, `s` untouched, when k exceeds the slots left
+ *     or `s` is one of the slots;
+ *   - the loop runs its self-contained steps (as with a term or a pending sensor plan): the fused steady-state launch never writes
+ *     the posterior covariance.  A filter without a recorder takes the launches it always took, and one whose recorder is cleared
+ *     gives the bits of a filter that never had one;
+ *   - `pnmol_state_destroy` of a slot returns -1 (clear the recorder first); `pnmol_filter_destroy` clears the recorder before its
+ *     own checks.
+ * fp64 filters, white-noise and latent-force, with or without a term, with or without a sensor plan; `pnmol_filter_step` records
+ * nothing.  Memory: the slots themselves (Dp^2 + 2 Dp doubles each) and count Dp doubles of scratch.
+ * `pnmol_filter_recorder_pending`: the cursor (the slot the next step fills) and the number of slots (0, 0: no recorder).
+ * `pnmol_filter_recorder_means`: the means of the filled slots [first, first + count) as (count, n, d_state) row-major, raw
+ * coordinates -- what `pnmol_state_get_mean` gives per state, gathered on the device and read back with one copy and one
+ * synchronisation.  -1: no recorder, a slot that has not been filled, an unfinished `pnmol_filter_steps_begin`. */
+int pnmol_filter_set_recorder(pnmol_filter* f, int count, pnmol_state* const* slots);
+int pnmol_filter_recorder_pending(const pnmol_filter* f, int* next, int* count);
+int pnmol_filter_recorder_means(pnmol_filter* f, int first, int count, double* means_cnd);
+
+/* The whole backward pass of the RTS smoother in one call: what T calls of `pnmol_smoother_step` compute (kalman.py:33-46 of the
+ * reference per step; the same kernels in the same order, so the same bits), for k = T-1 .. 0 enqueued back to back on the ctx
+ * stream with ONE synchronisation at the end instead of one per step, no state allocated per step and no mean read back per step.
+ * filt (T+1 states: the filtered trajectory, e.g. a recorder's slots behind the initial state), dt_T[k] = the step from filt[k] to
+ * filt[k+1].  Each step's sweep info word is kept on the device in a per-step array before the next step resets it.
+ * means_T1d / stds_T1d ((T+1, d) row-major, either may be NULL): the smoothed read-outs s0 m[j] and s0 sqrt(max(var_j, 0)) of
+ * derivative 0, written on the device by k_sm_readout with the arithmetic of the loop's read-out; row T is the terminal filtered
+ * state's.  out = NULL: the pass rotates two internal states (2 (Dp^2 + 2 Dp) doubles, allocated on the first such call and kept
+ * by the filter), so memory does not grow with T.  out (T+1 states): out[k] receives the smoothed state at filt[k]->t in the frame
+ * of dt_T[k], out[T] a copy of filt[T].
+ * Returns 0, or the -2 / -3 of the first failing step in backward order (`pnmol_last_error` names the step; info_T[k], optional,
+ * holds 0 / -2 / -3 per step); the outputs of the steps behind it (lower k) are undefined then.  -1 before anything is enqueued:
+ * the refusals of `pnmol_smoother_step` (null, foreign state, dt <= 0, latent-force or fp32 filter), T < 1, a state listed twice
+ * in out, a state of out that is one of filt.  -4: out of memory.  No bridges are made: dense output keeps
+ * `pnmol_smoother_step_bridge`. */
+int pnmol_smoother_steps(pnmol_filter* f, int T, pnmol_state* const* filt, const double* dt_T, pnmol_state* const* out,
+                         double* means_T1d, double* stds_T1d, int* info_T);
 
 /* Optional: do the one-off host work of a following `pnmol_filter_steps(f, s, k, dt, ...)` now
  * (output buffers, capture + instantiation of the hipGraphs the step loop is replayed from). */

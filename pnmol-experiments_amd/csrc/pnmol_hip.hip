@@ -3459,9 +3459,11 @@ enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 // The loop is not fused while a reaction is set: the fused loop makes the next step's z and G inside the previous step's
 // k_readout launch, before that step's re-linearisation could run.  The same holds while a sensor plan has pending entries
 // (pnmol_filter_set_observations): z and G of the step behind an update would come from the unconditioned state, and the fused
-// steps write P only in the call's last step, while the update conditions P itself.
+// steps write P only in the call's last step, while the update conditions P itself.  Nor while a recorder is set
+// (pnmol_filter_set_recorder): it copies the posterior P behind every step, which the fused steady-state launch never writes.
 inline bool fused_loop(const pnmol_filter* f) {
-    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f) && !pnmol_observe_plan_pending(f);
+    return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f) && !pnmol_observe_plan_pending(f) &&
+           !pnmol_record_active(f);
 }
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
@@ -3640,13 +3642,15 @@ int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double 
 }
 
 // a step of the constant-step loop: with a reaction set the operator is re-linearised at this step's predicted mean first
-// (k_linearize, pnmol_reaction.hip)
+// (k_linearize, pnmol_reaction.hip); with a recorder set the state behind the step goes into its slot (k_record, pnmol_record.hip;
+// keep = false: a sensor update follows at once and the caller records behind it)
 int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
-              double* varout, StepKind kind) {
+              double* varout, StepKind kind, bool keep = true) {
     if (has_term(f)) {
         if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt)) return rc;
     }
-    return dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind);
+    if (int rc = dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind)) return rc;
+    return keep ? pnmol_record_enqueue(f, Pout, mout, varout) : 0;
 }
 
 void drop_graphs(pnmol_filter* f) {
@@ -4286,6 +4290,12 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
 
 int pnmol_filter_destroy(pnmol_filter* f) {
     if (!f) return -1;
+    if (pnmol_record_active(f) && !f->pending_state) {  // (the recorder goes first: its slots are states, destroyed only without it)
+        hipSetDevice(f->ctx->device);
+        (void)hipStreamSynchronize(f->ctx->stream);
+        drop_graphs(f);
+        pnmol_record_free(f);
+    }
     if (f->states.load() != 0) {  // (lifetime rule, include/pnmol_hip.h: states first)
         f->ctx->err = "pnmol_filter_destroy: " + std::to_string(f->states.load()) + " state(s) of this filter are still alive";
         return -1;
@@ -4318,6 +4328,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_dense_free_ws(f);
     pnmol_observe_free_ws(f);
     pnmol_observe_plan_free(f);
+    pnmol_record_free(f);
     pnmol_reaction_free_ws(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
@@ -4503,6 +4514,10 @@ int pnmol_state_destroy(pnmol_state* s) {
     if (!s) return -1;
     if (s->f->pending_state == s) {
         s->f->ctx->err = "pnmol_state_destroy: this state is the target of an unfinished pnmol_filter_steps_begin";
+        return -1;
+    }
+    if (pnmol_record_holds(s)) {
+        s->f->ctx->err = "pnmol_state_destroy: this state is a slot of the recorder its filter has set (clear the recorder first)";
         return -1;
     }
     s->f->states.fetch_sub(1);
@@ -4784,9 +4799,12 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     }
     pnmol_ctx* ctx = f->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    // a recorder: enough slots left and s not among them -- or the refusal, before anything is enqueued
+    int rc = pnmol_record_begin(f, s, k);
+    if (rc != 0) return rc;
     // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
     std::vector<int> ob_entry;
-    int rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
+    rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
     if (rc != 0) return rc;
     const bool planned = pnmol_observe_plan_pending(f);
     struct PlanGuard {  // a call that fails before it is enqueued in full leaves no bookkeeping behind
@@ -4798,6 +4816,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     if (rc != 0) return rc;
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
+    if ((rc = pnmol_record_enqueue_cursor(f)) != 0) return rc;
     if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
@@ -4813,9 +4832,11 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     // the buffer a captured graph starts from (prepare_graphs): with a plan the eager steps around the updates move the parity
     double* const graphP0 = (s->frame_dt != dt || fused) ? f->tmpP : s->P;
     // the update of the plan entry mapped behind step j (if any), in place on the buffers that hold the state there
+    // (a recorder: the slot of step j takes the conditioned state -- the step counter still names it)
     const auto update_behind = [&](int j) {
         if (!planned || ob_entry[(size_t)j] < 0) return 0;
-        return pnmol_observe_plan_enqueue(f, ob_entry[(size_t)j], curP, curM, s->var, dt, j);
+        if (int urc = pnmol_observe_plan_enqueue(f, ob_entry[(size_t)j], curP, curM, s->var, dt, j)) return urc;
+        return pnmol_record_enqueue(f, curP, curM, s->var);
     };
     int it = 0;
     while (it < k) {
@@ -4841,7 +4862,8 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
             if ((rc = update_behind(it - 1)) != 0) return rc;
             continue;
         }
-        rc = loop_step(f, curP, curM, frame, dt, nxtP, nxtM, s->var, !fused ? STEP_FULL : (it == 0 ? STEP_FIRST : STEP_STEADY));
+        rc = loop_step(f, curP, curM, frame, dt, nxtP, nxtM, s->var, !fused ? STEP_FULL : (it == 0 ? STEP_FIRST : STEP_STEADY),
+                       !(planned && ob_entry[(size_t)it] >= 0));
         if (rc != 0) return rc;
         double* t;
         t = curP, curP = nxtP, nxtP = t;
@@ -4904,6 +4926,7 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
         if (o.info >= 0 && bad < 0) bad = it;
         if (o.info == -2 && stuck < 0) stuck = it;
     }
+    pnmol_record_collect(f, s->t, k, dt);  // (a recorder: the call's slots take their times; the cursor moves, whatever failed)
     s->t = t;
     s->frame_dt = dt;
     // a sensor plan: the results of the entries this call applied; the cursor moves.  The update behind step j comes after step j
@@ -4950,8 +4973,10 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
     if (e == hipSuccess) e = hipMemcpyAsync(bak + nP + Dp, s->var, sizeof(double) * Dp, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) {
         const int ob_next = pnmol_observe_plan_cursor(f);  // (a sensor plan: the rehearsal applies entries; the cursor goes back)
+        const int rec_next = pnmol_record_cursor(f);       // (a recorder: the rehearsal fills slots the real call fills again)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
         pnmol_observe_plan_rewind(f, ob_next);
+        pnmol_record_rewind(f, rec_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

@@ -167,6 +167,12 @@ struct pnmol_filter {
     // ((3 Dp/32 + 1) * 32 x Dp), its L_jj^-1 tiles, feed tiles and flags, and G, C, Ps^h (Dp x Dp), [m^h | dm] (2 Dp)
     SweepWs sm_sweep;
     double *sm_gain = nullptr, *sm_C = nullptr, *sm_Psh = nullptr, *sm_vec = nullptr;
+    // The whole backward pass in one call (pnmol_smoother_steps), allocated on its first use: two states' worth of buffers
+    // ([P | mean | var], Dp^2 + 2 Dp doubles each) that a pass without `out` rotates, the device read-out [means | stds] of
+    // sm_ro_rows rows of d with the per-step info words behind them, and its pinned host image
+    double* sm_rot[2] = {nullptr, nullptr};
+    double *sm_ro = nullptr, *sm_ro_pin = nullptr;
+    int sm_ro_rows = 0;
     // Joint draws (pnmol_samples_*), allocated on first use: the square lenient sweep P^h -> C (sp_Gc, sp_F: Dp x Dp, its
     // L_jj^-1 tiles, feed tiles, flags, info word), Gamma (dp x dp, from the host copy kept at creation) and m^h (Dp).  The
     // main sweep of a backward step runs in the smoother's workspace above.
@@ -187,6 +193,10 @@ struct pnmol_filter {
     std::vector<ObserveWs*> ob_ws;
     // Sensor data in the constant-step loop (pnmol_filter_set_observations, pnmol_observe.hip): NULL = no plan
     struct ObservePlanDev* ob_plan = nullptr;
+    // The recorder of the constant-step loop (pnmol_filter_set_recorder, pnmol_record.hip): NULL = none.  While one is set the
+    // loop runs non-fused (the fused steady-state launch never writes the posterior covariance) and copies the state behind
+    // every step into the next slot
+    struct RecordDev* rec_plan = nullptr;
     // The nonlinear term the device linearises itself (pnmol_reaction.hip): none, a pointwise reaction (pnmol_filter_set_reaction),
     // a coupled system (pnmol_filter_set_reaction_system) or a convection term (pnmol_filter_set_convection), with the descriptor of
     // that kind.  While one is set the constant-step loop re-linearises in front of every step, runs non-fused and carries no error
@@ -293,6 +303,24 @@ void pnmol_observe_plan_abandon(pnmol_filter* f);
 int pnmol_observe_plan_cursor(const pnmol_filter* f);
 void pnmol_observe_plan_rewind(pnmol_filter* f, int next);
 void pnmol_observe_plan_free(pnmol_filter* f);
+
+// pnmol_record.hip: the recorder inside pnmol_filter_steps_begin / _end.  active: a recorder is set (the loop then runs non-fused).
+bool pnmol_record_active(const pnmol_filter* f);
+// s is a slot of the recorder its filter has set (pnmol_state_destroy refuses it)
+bool pnmol_record_holds(const pnmol_state* s);
+// the refusals of a call of k steps that advances s (-1, ctx->err set; nothing of HIP is touched)
+int pnmol_record_begin(pnmol_filter* f, const pnmol_state* s, int k);
+// the cursor word of the running call, on the ctx stream (once per call, in front of its steps)
+int pnmol_record_enqueue_cursor(pnmol_filter* f);
+// k_record behind a step (or behind the sensor update that follows it): the state in (P, mean, var) into the slot the device words
+// name.  The same arguments at every step of a buffer parity, so the launch may be captured.  No synchronisation.
+int pnmol_record_enqueue(pnmol_filter* f, const double* P, const double* mean, const double* var);
+// behind the call's synchronisation: the k slots take their times (t0 + dt, ...) and frame, the cursor moves
+void pnmol_record_collect(pnmol_filter* f, double t0, int k, double dt);
+// the cursor, and putting it back (pnmol_filter_prepare_steps rehearses a call)
+int pnmol_record_cursor(const pnmol_filter* f);
+void pnmol_record_rewind(pnmol_filter* f, int next);
+void pnmol_record_free(pnmol_filter* f);
 
 void pnmol_reaction_free_ws(pnmol_filter* f);
 // pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system, k_linearize_convection for a convection

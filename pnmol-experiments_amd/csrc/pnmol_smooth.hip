@@ -238,6 +238,52 @@ int smoother_step_impl(pnmol_filter* f, const pnmol_state* filt_k, const pnmol_s
     return rc;
 }
 
+// Row `row` of the smoothed read-outs of a whole backward pass (pnmol_smoother_steps), the arithmetic of the loop's k_readout:
+// s0 m[j] and s0 sqrt(max(var[j], 0)) of derivative 0.  Thread 0 also keeps the step's sweep info word, which the next step's
+// sweep resets (sweep_info = NULL: the terminal row, which no sweep made).
+__global__ __launch_bounds__(256) void k_sm_readout(const double* __restrict__ mean, const double* __restrict__ var, double s0,
+                                                    int d, double* __restrict__ means_row, double* __restrict__ stds_row,
+                                                    const int* __restrict__ sweep_info, int* __restrict__ info_step) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < d) {
+        means_row[j] = s0 * mean[j];
+        stds_row[j] = s0 * sqrt(fmax(var[j], 0.0));
+    }
+    if (j == 0 && sweep_info) *info_step = *sweep_info;
+}
+
+// the buffers of pnmol_smoother_steps: the read-out of `rows` rows (grown on demand) and, for a pass that keeps no states, the two
+// rotating ones
+int smoother_steps_ensure(pnmol_filter* f, int rows, bool rotate) {
+    pnmol_ctx* ctx = f->ctx;
+    const size_t Dp = (size_t)f->Dp;
+    if (rows > f->sm_ro_rows) {
+        if (f->sm_ro) (void)hipFree(f->sm_ro);
+        if (f->sm_ro_pin) (void)hipHostFree(f->sm_ro_pin);
+        f->sm_ro = f->sm_ro_pin = nullptr, f->sm_ro_rows = 0;
+        const size_t bytes = sizeof(double) * ((size_t)2 * rows * f->d + (size_t)rows);
+        hipError_t e = hipMalloc(&f->sm_ro, bytes);
+        if (e == hipSuccess) e = hipHostMalloc(&f->sm_ro_pin, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            if (f->sm_ro) (void)hipFree(f->sm_ro);
+            f->sm_ro = nullptr;
+            ctx->err = std::string("pnmol_smoother_steps: read-out buffers: ") + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? -4 : -2;
+        }
+        f->sm_ro_rows = rows;
+    }
+    for (int i = 0; rotate && i < 2; ++i)
+        if (!f->sm_rot[i]) {
+            const hipError_t e = hipMalloc(&f->sm_rot[i], sizeof(double) * (Dp * Dp + 2 * Dp));
+            if (e != hipSuccess) {
+                f->sm_rot[i] = nullptr;
+                ctx->err = std::string("pnmol_smoother_steps: rotating states: ") + hipGetErrorString(e);
+                return e == hipErrorOutOfMemory ? -4 : -2;
+            }
+        }
+    return 0;
+}
+
 }  // namespace
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
@@ -249,6 +295,11 @@ void pnmol_smooth_free_ws(pnmol_filter* f) {
     for (void* p : {(void*)f->sm_gain, (void*)f->sm_C, (void*)f->sm_Psh, (void*)f->sm_vec})
         if (p) (void)hipFree(p);
     f->sm_gain = f->sm_C = f->sm_Psh = f->sm_vec = nullptr;
+    for (void* p : {(void*)f->sm_rot[0], (void*)f->sm_rot[1], (void*)f->sm_ro})
+        if (p) (void)hipFree(p);
+    if (f->sm_ro_pin) (void)hipHostFree(f->sm_ro_pin);
+    f->sm_rot[0] = f->sm_rot[1] = f->sm_ro = f->sm_ro_pin = nullptr;
+    f->sm_ro_rows = 0;
 }
 
 int pnmol_smooth_ensure_ws(pnmol_filter* f) {
@@ -281,4 +332,106 @@ int pnmol_smoother_step_bridge(pnmol_filter* f, const pnmol_state* filt_k, const
         return -1;
     }
     return smoother_step_impl(f, filt_k, smooth_next, dt, out, keep_full, bridge);
+}
+
+// The whole backward pass: what T calls of pnmol_smoother_step compute, enqueued back to back with one synchronisation at the end.
+int pnmol_smoother_steps(pnmol_filter* f, int T, pnmol_state* const* filt, const double* dt_T, pnmol_state* const* out,
+                         double* means_T1d, double* stds_T1d, int* info_T) {
+    if (!f) return -1;
+    pnmol_ctx* ctx = f->ctx;
+    const auto refuse = [&](const std::string& why) {
+        ctx->err = "pnmol_smoother_steps: " + why;
+        return -1;
+    };
+    if (T < 1 || !filt || !dt_T) return refuse("bad argument (T < 1, or no filtered states, or no step sizes)");
+    if (f->ds != f->d || f->p32) return refuse("bad argument (latent-force or fp32 filter)");
+    for (int k = 0; k <= T; ++k) {
+        if (!filt[k] || (out && !out[k])) return refuse("bad argument (null state at index " + std::to_string(k) + ")");
+        if (filt[k]->f != f || (out && out[k]->f != f)) return refuse("bad argument (foreign state at index " + std::to_string(k) + ")");
+    }
+    for (int k = 0; k < T; ++k)
+        if (!(dt_T[k] > 0.0)) return refuse("bad argument (dt <= 0 at step " + std::to_string(k) + ")");
+    if (out) {
+        std::vector<const pnmol_state*> in(filt, filt + T + 1), res(out, out + T + 1);
+        std::sort(in.begin(), in.end());
+        std::sort(res.begin(), res.end());
+        if (std::adjacent_find(res.begin(), res.end()) != res.end()) return refuse("bad argument (aliasing: a state listed twice in out)");
+        for (const pnmol_state* s : res)
+            if (std::binary_search(in.begin(), in.end(), s)) return refuse("bad argument (aliasing: a state of out is one of filt)");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = pnmol_smooth_ensure_ws(f);
+    if (rc != 0) return rc;
+    if ((rc = smoother_steps_ensure(f, T + 1, out == nullptr)) != 0) return rc;
+    const long Dp = f->Dp;
+    const int d = f->d, rows = T + 1;
+    const size_t sq = (size_t)Dp * Dp;
+    double *ro_means = f->sm_ro, *ro_stds = f->sm_ro + (size_t)rows * d;
+    int* ro_info = reinterpret_cast<int*>(f->sm_ro + (size_t)2 * rows * d);
+    const unsigned rblocks = (unsigned)((d + 255) / 256);
+    const SweepWs& sw = f->sm_sweep;
+    double *mh = f->sm_vec, *dm = f->sm_vec + Dp;
+    const double* V = sw.F + Dp * Dp;
+    const double* T_ = sw.F + (2 * Dp + NB) * Dp;
+    SmoothConsts c{};
+    std::memcpy(c.A1, f->iwp.A1, sizeof(c.A1));
+    std::memcpy(c.Q1, f->iwp.Q1, sizeof(c.Q1));
+
+    // row T: the terminal filtered state (a copy of it in out[T])
+    const pnmol_state* last = filt[T];
+    const double *nP = last->P, *nM = last->mean, *nV = last->var;
+    double nframe = last->frame_dt;
+    if (out) {
+        HIPCHK(ctx, hipMemcpyAsync(out[T]->P, last->P, sizeof(double) * sq, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(out[T]->mean, last->mean, sizeof(double) * Dp, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(out[T]->var, last->var, sizeof(double) * Dp, hipMemcpyDeviceToDevice, st));
+    }
+    k_sm_readout<<<rblocks, 256, 0, st>>>(nM, nV, nframe == 0.0 ? 1.0 : nordsieck_scale(f->nu, 0, nframe), d,
+                                          ro_means + (size_t)T * d, ro_stds + (size_t)T * d, nullptr, nullptr);
+    for (int k = T - 1; k >= 0; --k) {
+        const double dt = dt_T[k];
+        for (int a = 0; a < f->n; ++a) {
+            c.ts[a] = frame_ratio(f, a, filt[k]->frame_dt, dt);
+            c.tsn[a] = frame_ratio(f, a, nframe, dt);
+        }
+        double* base = out ? nullptr : f->sm_rot[(T - 1 - k) & 1];
+        double* oP = out ? out[k]->P : base;
+        double* oM = out ? out[k]->mean : base + sq;
+        double* oV = out ? out[k]->var : base + sq + Dp;
+        rc = launch_build(st, f->n, filt[k]->P, nP, filt[k]->mean, nM, f->Kg, c, f->d, f->dp, sw.G, oP, f->sm_Psh, mh, dm);
+        if (rc == 0) rc = sweep_ws_enqueue(f, sw, st, 0, "pnmol_smoother_steps");
+        if (rc == 0) rc = launch_finish(st, Dp, V, T_, f->sm_Psh, mh, dm, f->sm_gain, f->sm_C, oP, oM, oV);
+        if (rc == 0) {
+            k_sm_readout<<<rblocks, 256, 0, st>>>(oM, oV, nordsieck_scale(f->nu, 0, dt), d, ro_means + (size_t)k * d,
+                                                  ro_stds + (size_t)k * d, sw.info, ro_info + k);
+            if (hipGetLastError() != hipSuccess) rc = -2;
+        }
+        if (rc != 0) {
+            if (rc != -1) ctx->err = "pnmol_smoother_steps: kernel launch failed at step " + std::to_string(k);
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        nP = oP, nM = oM, nV = oV, nframe = dt;
+    }
+    const size_t bytes = sizeof(double) * ((size_t)2 * rows * d + (size_t)rows);
+    HIPCHK(ctx, hipMemcpyAsync(f->sm_ro_pin, f->sm_ro, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipGetLastError());
+    if (means_T1d) std::memcpy(means_T1d, f->sm_ro_pin, sizeof(double) * (size_t)rows * d);
+    if (stds_T1d) std::memcpy(stds_T1d, f->sm_ro_pin + (size_t)rows * d, sizeof(double) * (size_t)rows * d);
+    if (out) {
+        out[T]->t = last->t, out[T]->frame_dt = last->frame_dt;
+        for (int k = 0; k < T; ++k) out[k]->t = filt[k]->t, out[k]->frame_dt = dt_T[k];
+    }
+    const int* inf = reinterpret_cast<const int*>(f->sm_ro_pin + (size_t)2 * rows * d);
+    int first_rc = 0;
+    for (int k = T - 1; k >= 0; --k) {  // backward order: the first step that failed is the one with the largest k
+        const int code = inf[k] == -2 ? -2 : (inf[k] < Dp ? -3 : 0);
+        if (info_T) info_T[k] = code;
+        if (code != 0 && first_rc == 0)
+            first_rc = sweep_info_result(ctx, inf[k], Dp, ("pnmol_smoother_steps: step " + std::to_string(k)).c_str(),
+                                         "predicted covariance not positive definite", "a dependency wait of the sweep timed out");
+    }
+    return first_rc;
 }

@@ -120,6 +120,11 @@ SYMBOLS = {
                                           ctypes.POINTER(StepOut)]),
     "pnmol_filter_steps_begin": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double]),
     "pnmol_filter_steps_end": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, ctypes.POINTER(StepOut)]),
+    "pnmol_filter_set_recorder": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "pnmol_filter_recorder_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_filter_recorder_means": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "pnmol_smoother_steps": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp), _c_double_p, ctypes.POINTER(_vp),
+                                            _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]),
     "pnmol_filter_prepare_steps": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double]),
     "pnmol_filter_last_steps_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "pnmol_filter_prepare_error_model": (ctypes.c_int, [_vp, ctypes.c_double]),
@@ -321,8 +326,12 @@ class Filter:
         self._live = {}
         self._live_samples = {}     # the same for the pnmol_samples objects (Samples)
         self._live_bridges = {}     # ... and the pnmol_bridge objects (Bridge)
+        self._recorder = None       # the States a set recorder fills (`set_recorder`), kept alive while it is set
 
     def __del__(self):
+        if getattr(self, "_recorder", None) is not None and getattr(self, "handle", None):
+            self.lib.pnmol_filter_set_recorder(self.handle, 0, None)   # (the library refuses to destroy a recorder's slot)
+            self._recorder = None
         # The cyclic garbage collector (and interpreter shutdown) finalises a filter and its states in ANY order: the
         # states' handles go first here; a State finalised later finds its entry gone and does nothing (State._destroy).
         live = getattr(self, "_live", None)
@@ -505,6 +514,57 @@ class Filter:
         rc = self.lib.pnmol_state_observe_planned(self.handle, state.handle, int(index), ctypes.byref(res))
         self.ctx.check(rc, "pnmol_state_observe_planned")
         return res
+
+    def set_recorder(self, states):
+        """The recorder of the constant-step loop (`pnmol_filter_set_recorder`): `states[i]` (States of this filter) receives the
+        state behind the i-th step `steps` takes from now on, on the device; the cursor starts at slot 0.  The filter keeps the
+        states alive until `clear_recorder()` (the library refuses to destroy a slot)."""
+        states = list(states)
+        if not states:
+            raise ValueError("set_recorder needs at least one state (clear_recorder() drops the recorder)")
+        slots = (_vp * len(states))(*[None if s is None else s.handle for s in states])
+        self.ctx.check(self.lib.pnmol_filter_set_recorder(self.handle, len(states), slots), "pnmol_filter_set_recorder")
+        self._recorder = states
+
+    def clear_recorder(self):
+        """Drop the recorder: the filter then takes the launches and gives the bits of one that never had a recorder."""
+        self.ctx.check(self.lib.pnmol_filter_set_recorder(self.handle, 0, None), "pnmol_filter_set_recorder")
+        self._recorder = None
+
+    def recorder_pending(self):
+        """(next, count): the recorder's cursor -- the slot the next step fills -- and its number of slots ((0, 0): none)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.pnmol_filter_recorder_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
+                       "pnmol_filter_recorder_pending")
+        return nxt.value, n.value
+
+    def recorder_means(self, first=0, count=None):
+        """Means (count, n, d_state) of the filled slots [first, first + count) (default: up to the cursor), raw coordinates, in
+        one read-back (`pnmol_filter_recorder_means`)."""
+        if count is None:
+            count = self.recorder_pending()[0] - first
+        out = np.empty((max(int(count), 0), self.n, self.ds))
+        self.ctx.check(self.lib.pnmol_filter_recorder_means(self.handle, int(first), int(count), _dp(out)),
+                       "pnmol_filter_recorder_means")
+        return out
+
+    def smoother_steps(self, states, dts, keep=False):
+        """The whole RTS backward pass in one call (`pnmol_smoother_steps`): `states` the T+1 filtered States, `dts` the T steps
+        between them.  Returns (means (T+1, d), stds (T+1, d)) -- the smoothed read-outs of derivative 0 -- and, with keep=True,
+        a third element: the T+1 smoothed States (the last one a copy of the terminal filtered state)."""
+        states = list(states)
+        dts = _f64(np.atleast_1d(dts))
+        T = len(states) - 1
+        if T < 1 or dts.shape != (T,):
+            raise ValueError(f"smoother_steps needs T + 1 >= 2 states and T step sizes, got {len(states)} and {dts.shape}")
+        filt = (_vp * (T + 1))(*[None if s is None else s.handle for s in states])
+        out = [State(self) for _ in range(T + 1)] if keep else None
+        outs = None if out is None else (_vp * (T + 1))(*[s.handle for s in out])
+        means, stds = np.empty((T + 1, self.d)), np.empty((T + 1, self.d))
+        info = (ctypes.c_int * T)()
+        rc = self.lib.pnmol_smoother_steps(self.handle, T, filt, _dp(dts), outs, _dp(means), _dp(stds), info)
+        self.ctx.check(rc, "pnmol_smoother_steps")
+        return (means, stds, out) if keep else (means, stds)
 
     def predict(self, state, dt):
         """The prior alone carried over dt > 0 from `state` (`pnmol_state_predict`): a new State at state.t + dt."""

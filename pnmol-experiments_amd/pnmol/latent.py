@@ -158,3 +158,6 @@ class SemiLinearLatentForceEK1(_LatentForceEK1Base):
 
     def solve_marginals(self, pde, *, num_steps=None, observations=None):
         raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
+
+    def solve_on_device(self, pde, *, num_steps=None, observations=None):
+        raise TypeError("solve_on_device keeps the loop on the device and needs a linear PDE; use solve()")

@@ -391,6 +391,92 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         info = dict(num_steps=len(dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
         return out + (info,)
 
+    # ------------------------------------------------------------------ the device loop with the trajectory kept
+    def solve_on_device(self, pde, *, num_steps=None, observations=None):
+        """`solve()` of the `Constant` rule through the device-resident loop: a `PDESolution` with the time grid of
+        `solve_marginals` (a runt last step included), `mean` (T+1, n, d_state), device-resident states, the calibrated
+        diffusion as `solve()` computes it and `info = dict(num_steps)` -- with `observations` (as in `solve_marginals`) also
+        `data_log_likelihood` / `data_log_likelihoods`.  `smooth`, `smooth_marginals`, `sample`, `sample_dense`, `solution(t)` and
+        `state_at` work on it as on a `solve()` result.
+
+        The loop records the state behind every step into one device state per grid time (`pnmol_filter_set_recorder`, DESIGN.md
+        section 20): no host round trip per step, one read-back of all means per run of equal steps.  It accepts what
+        `solve_marginals` accepts (linear problems, problems whose term the device linearises, one sensor array) in the fp64
+        covariance form; memory: T + 1 states of (n d)^2 doubles on the device."""
+        from . import data, sqrtform
+
+        if not isinstance(self.steprule, _step.Constant):
+            raise TypeError("solve_on_device needs the Constant step rule")
+        if isinstance(self, sqrtform._SqrtFormMixin) or self.dtype != "f64":
+            raise TypeError(f"solve_on_device() supports the fp64 covariance-form solvers of pnmol.white and pnmol.latent; "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
+        obs, dt0 = None, self.steprule.first_dt(pde)
+        if observations is not None:                            # everything is validated before `initialize` binds the device
+            self._check_observations_supported()
+            obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
+        ts, dts = self._constant_schedule(pde, num_steps)
+        if obs:
+            times, C, R, ys = data.shared_sensors(obs)
+            if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
+                raise ValueError(f"observation at t={times[-1]} lies behind the last step taken (t={ts[-1]}, {len(dts)} steps)")
+        state = self.initialize(pde)
+        flt = self._device_filter
+        lls = []
+        if obs and data.times_agree(obs[0].t, pde.t0, dt0):     # at t0: the initial state, as solve() does it
+            state, ll = self._observe(state, obs[0])
+            lls.append(ll)
+            times, ys = times[1:], ys[1:]
+        first = state.y
+        slots = [flt.new_state() for _ in dts]
+        planned = False
+        try:
+            if obs and times.size:
+                Cd = C if C.shape[1] == flt.ds else np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
+                flt.set_observations(times, Cd, ys, R)
+                planned = True
+            sig = np.zeros(0)
+            if slots:
+                flt.set_recorder(slots)
+                # (the loop advances its state in place: it works on a copy, the initial state stays what `ys[0]` holds)
+                work = state._replace(y=rv.DeviceMultivariateNormal(first.mean, first.device_state.clone()))
+                _, _, _, sig, _ = self._run_device_loop(pde, work, ts, dts)
+                filled, count = flt.recorder_pending()
+                if filled != count:
+                    raise RuntimeError(f"{count - filled} step(s) of the loop were not recorded")
+                means = flt.recorder_means(0, count)            # one read-back for all states
+            else:
+                means = np.zeros((0,) + first.mean.shape)
+            if planned:
+                applied, nobs = flt.observations_pending()
+                if applied != nobs:
+                    raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
+                lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
+        finally:
+            for clear in (flt.clear_recorder, flt.clear_observations if planned else None):
+                try:                                            # (a failure above is the one to report, not one of the clear)
+                    if clear is not None:
+                        clear()
+                except _hip.PnmolHipError:
+                    pass
+        states = [first] + [rv.DeviceMultivariateNormal(m, s) for m, s in zip(means, slots)]
+        info = dict(num_steps=len(dts))
+        if obs is not None:
+            info.update(data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
+        return pdefilter.PDESolution(t=np.array(ts), mean=np.stack([y.mean for y in states]), ys=states, info=info,
+                                     diffusion_squared_calibrated=np.mean(np.array(sig)))
+
+    def smooth_marginals(self, solution):
+        """(means (T+1, d), stds (T+1, d)): the read-out of `smooth(solution, dense=None)` -- smoothed mean and marginal std of
+        the PDE solution per grid time, uncalibrated -- through one `pnmol_smoother_steps` call: the whole backward pass enqueued
+        at once, one synchronisation, no smoothed state kept (two internal ones rotate).  `solution`: a `solve()` or
+        `solve_on_device()` result, unchanged.  Supported: what `smooth` supports."""
+        ys, flt = self._walk_inputs("smooth_marginals", solution)
+        t = np.asarray(solution.t, dtype=np.float64)
+        if len(ys) < 2:
+            y = ys[0]
+            return y.mean[:1, :flt.d].copy(), np.sqrt(np.maximum(y.marginal_var[:1, :flt.d], 0.0))
+        return flt.smoother_steps([y.device_state for y in ys], np.diff(t))
+
     # ------------------------------------------------------------------ backward walks (smoothing, joint draws)
     def _walk_inputs(self, who, solution):
         """What `smooth`, `sample` and `sample_dense` walk backwards: (the device-resident states of `solution`, the one filter
@@ -587,3 +673,8 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
         return super().solve_marginals(pde, num_steps=num_steps, observations=observations)
+
+    def solve_on_device(self, pde, *, num_steps=None, observations=None):
+        if self._reaction_for_device(pde) is None:
+            raise TypeError("solve_on_device keeps the loop on the device and needs a linear PDE; use solve()")
+        return super().solve_on_device(pde, num_steps=num_steps, observations=observations)
