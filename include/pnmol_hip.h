@@ -101,8 +101,8 @@ typedef struct pnmol_filter_desc {
 
 int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_filter** out);
 int pnmol_filter_destroy(pnmol_filter* f); /* -1, nothing freed, while states of f are alive (see Lifetimes) */
-/* Which sweep launch this filter's steps use (build-side diagnostic; no reference counterpart): *kernel = 0 per-panel
- * launches, 1 left-looking dataflow kernel (wide matrices: N = 1024, 2-d meshes), 2 register-resident right-looking kernel
+/* Which sweep launch this filter's steps use (build-side diagnostic; no reference counterpart): *kernel is 1 or 2:
+ * 1 left-looking dataflow kernel (wide matrices: N = 1024, 2-d meshes), 2 register-resident right-looking kernel
  * (d + nB <= 544); *xcd_home = the XCD its critical workgroups are placed on (XCD-local layout: the first such filter alive on
  * a device, or PNMOL_HIP_SWEEP_XL=1) or -1 (spread layout).  Timings of the two layouts differ; benchmarks report this. */
 int pnmol_filter_sweep_layout(const pnmol_filter* f, int* kernel, int* xcd_home);

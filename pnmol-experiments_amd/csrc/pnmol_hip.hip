@@ -252,192 +252,11 @@ __device__ __forceinline__ double bcast_lane(double x, int src) {
 //
 
 // ------------------------------------------------------------------------------------------
-// Two-wave variant of the 32x32 Cholesky + inverse (the one the step uses).
-// Wave 0 factorises: lane (i, h) = (l & 31, l >> 5) holds row i's columns of parity h, u[q] = A[i][2q+h], so one
-// FMA instruction updates two columns.  Column step J: the pivot is already known as a wave-uniform scalar (it was
-// predicted during step J-1 by one scalar FMA), column J is scaled and published to LDS (col[J], permuted so that
-// each half reads its multipliers with ds_read_b128 broadcasts), the next pivot is predicted from two
-// v_readlanes, and the general update reads the row multiplier and the column multipliers back from LDS -- that
-// LDS round trip overlaps the rsqrt chain of the next column instead of sitting in it.
-// Wave 1 builds L^-1 one column behind: it applies the same elementary operations to the identity
-// (Y = X^T, same layout), taking 1/sqrt(pivot) and the column multipliers from LDS once flag[J] is set.
-// Wave 0 never waits for wave 1, so there is no deadlock; each column has its own LDS buffer (no reuse hazard).
-// ------------------------------------------------------------------------------------------
-#ifdef PNMOL_STAMP
-__device__ unsigned long long pnmol_stamp_out[40];
-#define pnmol_stamp pnmol_stamp_out
-#endif
-struct Diag2wLds {
-    double col[NB][NB];   // col[J][pi(k)] = L[k][J]  (pi(k) = 16*(k&1) + (k>>1))
-    double dump[NB];      // where the half that does not own column J writes (keeps the stream branch-free)
-    double rs[NB];        // 1/sqrt(pivot J) or 0
-    double piv[NB];       // pivot J
-    int flag[NB];         // column J of `col`/`rs` is published
-};
-
-// value of x held by the 32-lane half HJ, delivered to both halves (v_permlane32_swap: VALU latency, no LDS)
-template <int HJ>
-__device__ __forceinline__ double from_half(double x) {
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const u2 rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);  // [0]: lanes 0..31 everywhere, [1]: lanes 32..63
-    const u2 rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double((int)rh[HJ], (int)rl[HJ]);
-}
-
-// u[q] -= m * L[2q+h][J] for the columns 2q+h > J of this lane's parity; the multiplier of column J+1 (`bnext`,
-// wave-uniform, only meaningful when HAVE_NEXT) does not go through LDS: it feeds the critical path.
-template <int J, bool HAVE_NEXT>
-__device__ __forceinline__ void diag2w_update(double (&u)[NB / 2], const double* __restrict__ colJ, double nm, int h,
-                                              double bnext) {
-#pragma unroll
-    for (int q = ((J + 1) >> 1) & ~1; q < NB / 2; q += 2) {
-        const double2 b = *reinterpret_cast<const double2*>(colJ + h * 16 + q);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int qq = q + t;
-            const double bv = t ? b.y : b.x;
-            if (2 * qq > J) {  // both parities of this register are right of column J
-                if (HAVE_NEXT && 2 * qq == J + 1) u[qq] = fma(nm, h ? bv : bnext, u[qq]);          // (J odd) k = J+1 on h = 0
-                else if (HAVE_NEXT && 2 * qq + 1 == J + 1) u[qq] = fma(nm, h ? bnext : bv, u[qq]);  // unreachable (2qq > J)
-                else u[qq] = fma(nm, bv, u[qq]);
-            } else if (2 * qq + 1 > J) {  // J == 2 qq: only the odd column 2qq+1 = J+1 is updated
-                u[qq] = h ? fma(nm, HAVE_NEXT ? bnext : bv, u[qq]) : u[qq];
-            }
-        }
-    }
-}
-
-template <int J>
-__device__ __forceinline__ void diag2w_factor_col(double (&u)[NB / 2], double& p, Diag2wLds* L, int lane, int pi_i,
-                                                  double thrv) {
-    constexpr int qJ = J >> 1, hJ = J & 1;
-    const int h = lane >> 5;
-#ifdef PNMOL_STAMP
-    pnmol_stamp[J] = __builtin_amdgcn_s_memtime();
-#endif
-    // Only  rsq -> refine -> (a[J+1][J] * rs) -> fma  is on the pivot-to-pivot chain; everything that does not
-    // need 1/sqrt(p) (pivot test, broadcasts of the still unscaled entries) is issued beside it.
-    const double y0 = __builtin_amdgcn_rsq(p);
-    const bool ok = p > bcast_lane(thrv, J);
-    double an = 0.0, aold = 0.0;
-    if constexpr (J + 1 < NB) {
-        an = bcast_lane(u[qJ], (J + 1) + 32 * hJ);                               // A[J+1][J], unscaled
-        aold = bcast_lane(u[(J + 1) >> 1], (J + 1) + 32 * ((J + 1) & 1));        // A[J+1][J+1]
-    }
-    const double e = fma(-(p * y0), y0, 1.0);
-    const double y = fma(y0 * e, fma(0.375, e, 0.5), y0);
-    const double rs = ok ? y : 0.0;
-    const double pj = p;
-    if constexpr (J + 1 < NB) {
-        const double sj = an * rs;  // = L[J+1][J]
-        p = fma(-sj, sj, aold);     // next pivot (the same FMA the general update performs on that element)
-        const double vj = u[qJ] * rs;
-        const bool own = (h == hJ);
-        u[qJ] = own ? vj : u[qJ];
-        (own ? &L->col[J][0] : &L->dump[0])[pi_i] = vj;
-        L->rs[J] = rs;  // wave-uniform values: every lane stores the same word (no divergent branch in the stream)
-        L->piv[J] = pj;
-        asm volatile("" ::: "memory");
-        __hip_atomic_store(&L->flag[J], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const double m = from_half<hJ>(vj);  // row multiplier L[i][J] for both halves
-        diag2w_update<J, true>(u, L->col[J], -m, h, sj);
-    } else {
-        const double vj = u[qJ] * rs;
-        u[qJ] = (h == hJ) ? vj : u[qJ];
-        L->rs[J] = rs;
-        L->piv[J] = pj;
-        asm volatile("" ::: "memory");
-        __hip_atomic_store(&L->flag[J], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-#ifndef PNMOL_NO_COLBARRIER
-#pragma unroll
-    for (int q = 0; q < NB / 2; ++q) asm volatile("" : "+v"(u[q]));
-#endif
-}
-
-template <int J>
-__device__ __forceinline__ void diag2w_inverse_col(double (&u)[NB / 2], Diag2wLds* L, int lane, int pi_c) {
-    constexpr int qJ = J >> 1, hJ = J & 1;
-    const int h = lane >> 5;
-    while (__hip_atomic_load(&L->flag[J], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-    const double rs = L->rs[J];
-    const double yj = u[qJ] * rs;
-    const bool own = (h == hJ);
-    u[qJ] = own ? yj : u[qJ];
-    if constexpr (J + 1 < NB) {
-        const double m = from_half<hJ>(yj);
-        diag2w_update<J, false>(u, L->col[J], -m, h, 0.0);
-    }
-#ifndef PNMOL_NO_COLBARRIER
-#pragma unroll
-    for (int q = 0; q < NB / 2; ++q) asm volatile("" : "+v"(u[q]));
-#endif
-}
-
-template <int... Js>
-__device__ __forceinline__ void diag2w_factor_all(double (&u)[NB / 2], double& p, Diag2wLds* L, int lane, int pi_i,
-                                                  double thrv, std::integer_sequence<int, Js...>) {
-    (diag2w_factor_col<Js>(u, p, L, lane, pi_i, thrv), ...);
-}
-template <int... Js>
-__device__ __forceinline__ void diag2w_inverse_all(double (&u)[NB / 2], Diag2wLds* L, int lane, int pi_c,
-                                                   std::integer_sequence<int, Js...>) {
-    (diag2w_inverse_col<Js>(u, L, lane, pi_c), ...);
-}
-
-// Called by waves 0 and 1 of a workgroup (wave = 0/1) after T holds the symmetric tile and a __syncthreads() that
-// also covers the zeroing of L->flag.  Writes L (upper zeroed) to Fd (leading dim ld) and L^-1 to Li (32x32).
-// `sdiag_blk` = the 32 original diagonal entries of this block.  WT: L^-1 is read by OTHER workgroups of the same
-// launch (k_sweep), so it leaves through agent-scope (write-through) stores.
-template <bool WT = false>
-__device__ __forceinline__ void diag2w_from_lds(const double* T, double* __restrict__ Fd, long ld,
-                                                double* __restrict__ Li, int wave, int lane, int* info, int base,
-                                                const double* sdiag_blk, double smax, Diag2wLds* L) {
-    const int i = lane & 31, h = lane >> 5;
-    const int pi_i = 16 * (i & 1) + (i >> 1);
-    double u[NB / 2];
-    if (wave == 0) {
-        const double sdv = fabs(sdiag_blk[i]);
-        const double thrv = 1e-13 * sdv;
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) u[q] = T[i * TLD + 2 * q + h];
-        double p = T[0];
-        diag2w_factor_all(u, p, L, lane, pi_i, thrv, std::make_integer_sequence<int, NB>{});
-#ifdef PNMOL_STAMP
-        pnmol_stamp[32] = __builtin_amdgcn_s_memtime();
-#endif
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) {
-            double2* dst = nullptr;
-            (void)dst;
-            Fd[(long)i * ld + 2 * q + h] = (2 * q + h <= i) ? u[q] : 0.0;
-        }
-        if (lane < NB) {
-            const double pv = L->piv[lane];
-            const bool fatal = !(pv > thrv) && (!(pv == pv) || (pv < -1e-3 * sdv && sdv > 1e-12 * smax));
-            const unsigned long long mk = __ballot(fatal);
-            if (mk != 0 && lane == 0) atomicMin(info, base + __builtin_ctzll(mk));
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) u[q] = (2 * q + h == i) ? 1.0 : 0.0;
-        diag2w_inverse_all(u, L, lane, pi_i, std::make_integer_sequence<int, NB>{});
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) {  // u[q] = Y[i][2q+h] = Linv[2q+h][i]
-            if constexpr (WT) __hip_atomic_store(&Li[(2 * q + h) * NB + i], u[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else Li[(2 * q + h) * NB + i] = u[q];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Four-wave, 4-column-blocked variant of the 32x32 Cholesky + inverse (the one k_sweep uses).
+// Four-wave, 4-column-blocked 32x32 Cholesky + inverse (the one the sweep kernels use).
 //
-// The column-at-a-time scheme above spends ~60 instructions per pivot, 43 of them fixed overhead (publication,
-// broadcasts, pivot chain): 5.3 us per block, and 17 blocks in a row are the critical path of the whole filter step.
-// Here a step eliminates FOUR columns:
+// A column-at-a-time scheme (the retired two-wave factorisation) spends ~60 instructions per pivot, 43
+// of them fixed overhead (publication, broadcasts, pivot chain): 5.3 us per block, and 17 blocks in a row are the critical
+// path of the whole filter step.  Here a step eliminates FOUR columns:
 //   * the tile lives in MFMA accumulators, NEGATED (n = -T) and symmetric, one 16x16 quadrant per wave as it falls
 //     out of the sweep's own accumulation (no LDS staging).  Read "transposed", accumulator register c of a
 //     quadrant IS the 4-column panel c in MFMA operand layout: lane (row, k) holds T[row][4c + k];
@@ -451,7 +270,7 @@ __device__ __forceinline__ void diag2w_from_lds(const double* T, double* __restr
 // register hand-over; w1 gives its quadrant (0,1) to w3 and then builds L^-1 one step behind (same elementary block
 // operations applied to the identity); w2 is free (publishes the row's last tile in k_sweep) and finally writes L.
 // Waves talk through LDS buffers that are written once per block (no reuse hazard) + flags; w0 never waits.
-// Semi-definite pivots: as above (rs = 0 -> zero column of L, zero row/column of L^-1).
+// Semi-definite pivots: the rule in front of this block (rs = 0 -> zero column of L, zero row/column of L^-1).
 // ------------------------------------------------------------------------------------------
 struct Diag4Lds {
     double x0[4][64];   // step c < 4: X panel rows 0..15, masked to row >= column, operand layout (lane = row + 16 k)
@@ -694,31 +513,11 @@ __device__ __forceinline__ void diag4_factor(const d4& nq, Diag4Lds* L, int w, i
     }
 }
 
-// this wave's quadrant (w >> 1, w & 1) of -T from a symmetric tile in LDS (leading dimension TLD), lower entries only
-__device__ __forceinline__ d4 diag4_quadrant_from_lds(const double* T, int w, int lane) {
-    const int fr = lane & 15, fk = lane >> 4, qi = w >> 1, qj = w & 1;
-    d4 n;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 16 * qi + fk + 4 * r, col = 16 * qj + fr;
-        n[r] = -(row >= col ? T[row * TLD + col] : T[col * TLD + row]);
-    }
-    return n;
-}
-
-__device__ __forceinline__ void tile_g2s(const double* __restrict__ g, long ld, double* s, int tid) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int e = tid + 256 * q, r = e >> 5, cc = e & 31;
-        s[r * TLD + cc] = g[(long)r * ld + cc];
-    }
-}
-
 // ------------------------------------------------------------------------------------------
-// K2  build the tall matrix G = [S; P- H^T; z^T; I].  Roles by blockIdx.y:
+// K2  build the rows [S; P- H^T] of the tall matrix G = [S; P- H^T; z^T; I]  (z^T: k_predict; I: k_set_identity, once).
+// Roles by blockIdx.y:
 //   [0, Dp)             row of P- H^T                       (stencil gather along the row of P-)
 //   [Dp, Dp+mp)         row of S = H P- H^T + R             (straight from P-, see s_entry)
-//   [Dp+mp, Dp+2mp)     row of the trailing identity block  (the sweep turns it into Ls^-T)
 // ------------------------------------------------------------------------------------------
 template <typename PT>
 __device__ __forceinline__ void front_block(const PT* __restrict__ Ppred, double* __restrict__ G,
@@ -744,26 +543,21 @@ __device__ __forceinline__ void front_block(const PT* __restrict__ Ppred, double
         }
         return;
     }
-    if (y < Dp + mp) {
-        const int ip = (int)(y - Dp);
-        // Only the block-lower part of S is ever read (a row block of the sweep uses its tiles up to the diagonal one,
-        // and inside a diagonal tile the entries right of the diagonal do not influence the factor): skip the rest.
-        if (i < mp && i < (ip / NB + 1) * NB) {
-            double v;
-            if (narrow && ip < mm.m && i < mm.m) {
-                HRow rr, rc;
-                h_row_load(mm, ip, rr);
-                h_row_load(mm, i, rc);
-                v = s_entry_w<HW>(Ppred, Dp, mm, rr, rc, ip, i, rdiag, Rdense);
-            } else {
-                v = s_entry(Ppred, Dp, mm, ip, i, rdiag, Rdense);
-            }
-            G[(long)ip * mp + i] = v;
+    const int ip = (int)(y - Dp);
+    // Only the block-lower part of S is ever read (a row block of the sweep uses its tiles up to the diagonal one,
+    // and inside a diagonal tile the entries right of the diagonal do not influence the factor): skip the rest.
+    if (i < mp && i < (ip / NB + 1) * NB) {
+        double v;
+        if (narrow && ip < mm.m && i < mm.m) {
+            HRow rr, rc;
+            h_row_load(mm, ip, rr);
+            h_row_load(mm, i, rc);
+            v = s_entry_w<HW>(Ppred, Dp, mm, rr, rc, ip, i, rdiag, Rdense);
+        } else {
+            v = s_entry(Ppred, Dp, mm, ip, i, rdiag, Rdense);
         }
-        return;
+        G[(long)ip * mp + i] = v;
     }
-    const long q = y - Dp - mp;
-    if (i < mp) G[((long)mp + Dp + NB + q) * mp + i] = (q == i) ? 1.0 : 0.0;
 }
 
 // The same rows of G by FEW, FAT workgroups (the constant-step loop's k_readout launch, where this gather is serial with the
@@ -865,105 +659,6 @@ __global__ __launch_bounds__(256) void k_front_s(double* __restrict__ G, const d
     G[(long)ip * mp + i] = v;
 }
 
-// first diagonal block: diag(S) -> sdiag, its max -> sdiag[mp]; F[0,0] = chol(G[0,0]), Linv[0] = its inverse
-__global__ __launch_bounds__(128) void k_diag0(const double* __restrict__ G, double* __restrict__ F,
-                                               double* __restrict__ Linv, int ld, int* info_base,
-                                               double* __restrict__ sdiag, const int* __restrict__ ctr) {
-    __shared__ double sT[NB * TLD];
-    __shared__ __attribute__((aligned(16))) Diag2wLds dl;
-    __shared__ double smx[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double smax = 0.0;
-    for (int e = tid; e < ld; e += 128) {
-        const double x = G[(long)e * ld + e];
-        sdiag[e] = x;
-        smax = fmax(smax, fabs(x));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) smax = fmax(smax, __shfl_xor(smax, o));
-    if (lane == 0) smx[wave] = smax;
-    if (tid < NB) dl.flag[tid] = 0;
-    for (int e = tid; e < NB * NB; e += 128) sT[(e >> 5) * TLD + (e & 31)] = G[(long)(e >> 5) * ld + (e & 31)];
-    __syncthreads();
-    smax = fmax(smx[0], smx[1]);
-    if (tid == 0) sdiag[ld] = smax;
-    diag2w_from_lds(sT, F, ld, Linv, wave, lane, info_base + (*ctr - 1), 0, sdiag, smax, &dl);
-}
-
-// panel j:  L_Ij = G_Ij Linv_j^T  for all row blocks I > j  (written to F by the c == 0 column),
-//           G_IK -= L_Ij L_Kj^T   for trailing column blocks K = j+1+c,
-//           and the workgroup owning (j+1, j+1) factorises it for the next panel.
-__global__ __launch_bounds__(256) void k_panel(double* __restrict__ G, double* __restrict__ F,
-                                               double* __restrict__ Linv, int ld, int j, int CB, int RBS,
-                                               int* info_base, const double* __restrict__ sdiag,
-                                               const int* __restrict__ ctr) {
-    // +2200 doubles of padding: A/B on one MI355X shows the latency-bound diagonal waves run ~2 % faster with at most
-    // three of these workgroups per CU (42.9 KB each) than with six (25 KB)
-    __shared__ __attribute__((aligned(16))) double smem_p[3 * NB * TLD + 2200];
-    double* sA = smem_p;
-    double* sB = smem_p + NB * TLD;
-    double* sI = smem_p + 2 * NB * TLD;
-    static_assert(sizeof(Diag2wLds) <= 2 * NB * TLD * sizeof(double), "Diag2wLds must fit in sB + sI");
-    Diag2wLds* dlp = reinterpret_cast<Diag2wLds*>(sB);  // sB and sI are free once the diagonal tile sits in sA
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-    const int I = j + 1 + blockIdx.x;
-    const int c = blockIdx.y;
-    const int Kc = j + 1 + c;
-    const bool trailing = Kc < CB;
-    if (trailing && I < RBS && I < Kc) return;  // strictly-upper tile of the symmetric part
-
-    const int wr = w >> 1, wc = w & 1;
-    const int fr = l & 15, fk = l >> 4;
-    // issue the loads of the tile to be updated first: their latency hides behind the panel product
-    double* gt = G + (long)I * NB * ld + (long)Kc * NB;
-    d4 acc = {0, 0, 0, 0};
-    if (trailing) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = gt[(long)(wr * 16 + fk + 4 * r) * ld + wc * 16 + fr];
-    }
-    tile_g2s(Linv + (long)j * NB * NB, NB, sI, tid);
-    tile_g2s(G + (long)I * NB * ld + (long)j * NB, ld, sA, tid);
-    if (trailing) tile_g2s(G + (long)Kc * NB * ld + (long)j * NB, ld, sB, tid);
-    __syncthreads();
-
-    d4 li = {0, 0, 0, 0}, lk = {0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < NB / 4; ++s) {
-        const double b = sI[(wc * 16 + fr) * TLD + 4 * s + fk];
-        li = __builtin_amdgcn_mfma_f64_16x16x4f64(sA[(wr * 16 + fr) * TLD + 4 * s + fk], b, li, 0, 0, 0);
-        if (trailing) lk = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[(wr * 16 + fr) * TLD + 4 * s + fk], b, lk, 0, 0, 0);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = wr * 16 + fk + 4 * r, col = wc * 16 + fr;
-        sA[row * TLD + col] = li[r];
-        if (trailing) sB[row * TLD + col] = lk[r];
-        if (c == 0) F[((long)I * NB + row) * ld + (long)j * NB + col] = li[r];
-    }
-    if (!trailing) return;
-    __syncthreads();
-
-#pragma unroll
-    for (int s = 0; s < NB / 4; ++s)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-sA[(wr * 16 + fr) * TLD + 4 * s + fk],
-                                                   sB[(wc * 16 + fr) * TLD + 4 * s + fk], acc, 0, 0, 0);
-    if (!(blockIdx.x == 0 && c == 0)) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gt[(long)(wr * 16 + fk + 4 * r) * ld + wc * 16 + fr] = acc[r];
-        return;
-    }
-    // next diagonal block (j+1, j+1): wave 0 factorises it for the next panel
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sA[(wr * 16 + fk + 4 * r) * TLD + wc * 16 + fr] = acc[r];
-    if (tid < NB) dlp->flag[tid] = 0;
-    __syncthreads();
-    if (w < 2)  // waves 0 and 1: factor / inverse (two-wave scheme above)
-        diag2w_from_lds(sA, F + ((long)(j + 1) * NB) * ld + (long)(j + 1) * NB, ld, Linv + (long)(j + 1) * NB * NB, w, l,
-                        info_base + (*ctr - 1), (j + 1) * NB, sdiag + (j + 1) * NB, sdiag[ld], dlp);
-}
-
 // ------------------------------------------------------------------------------------------
 // K3'  The whole sweep  G = [S; P-H^T; z^T; I]  ->  F = [Ls; W; r^T; Ls^-T]  in ONE launch (dataflow, left-looking).
 //
@@ -973,7 +668,7 @@ __global__ __launch_bounds__(256) void k_panel(double* __restrict__ G, double* _
 // Step j of row block I:   S_j = G_Ij - sum_{k<j} X_k L_jk^T   (needs row j of L;  X_k = F_Ik, own row)
 //                          X_j = S_j L_jj^-T                    (needs diag[j])
 // Chain rows (I < CB, the rows of S) stop at j = I-1, keep D = G_II - sum X_k X_k^T in registers and then factorise
-// D with the two-wave scheme above; the other rows (P-H^T, z, identity) run all CB steps.  G is only read.
+// D with the four-wave scheme above; the other rows (P-H^T, z, identity) run all CB steps.  G is only read.
 // Only  diag[j] -> (load L_jj^-1, two 8-MFMA products) -> factor(j+1) -> diag[j+1]  is on the critical path:
 // everything that needs only row j of L (published BEFORE block j is factorised) happens while block j is being
 // factorised, so a panel costs the 32x32 factorisation + one flag hop (~1.2 us, tools/flag_hop_bench.hip) instead of
@@ -3197,55 +2892,6 @@ __global__ void k_operator_diagonal(double* __restrict__ ell_val, const double* 
     shift[i] = op[d + i];
 }
 
-// Batched kernel finite-difference stencils (discretize.py:177-201): per mesh point p an s x s system
-//     w_p = (k(X_p, X_p) + eta I)^-1 Lk(x_p, X_p),     u_p = LLk(x_p, x_p) - w_p . Lk(x_p, X_p)
-// (X_p = the s stencil neighbours; the reference vmaps jnp.linalg.solve over the points).  One thread per point: LU with
-// partial pivoting in registers, like LAPACK's getf2 on the s x s matrix (same pivot rule, same update order).
-constexpr int FD_MAXS = 16;
-__global__ __launch_bounds__(128) void k_fd_solve(const double* __restrict__ gram, const double* __restrict__ dk,
-                                                  const double* __restrict__ llk, int N, int s, double* __restrict__ w,
-                                                  double* __restrict__ unc) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    double A[FD_MAXS][FD_MAXS], b[FD_MAXS];
-    for (int i = 0; i < s; ++i) {
-        for (int k = 0; k < s; ++k) A[i][k] = gram[((long)p * s + i) * s + k];
-        b[i] = dk[(long)p * s + i];
-    }
-    for (int c = 0; c < s; ++c) {
-        int piv = c;
-        double best = fabs(A[c][c]);
-        for (int i = c + 1; i < s; ++i)
-            if (fabs(A[i][c]) > best) best = fabs(A[i][c]), piv = i;
-        if (piv != c) {
-            for (int k = 0; k < s; ++k) {
-                const double t = A[c][k];
-                A[c][k] = A[piv][k], A[piv][k] = t;
-            }
-            const double t = b[c];
-            b[c] = b[piv], b[piv] = t;
-        }
-        const double inv = 1.0 / A[c][c];
-        for (int i = c + 1; i < s; ++i) {
-            const double f = A[i][c] * inv;
-            A[i][c] = f;
-            for (int k = c + 1; k < s; ++k) A[i][k] -= f * A[c][k];
-        }
-    }
-    for (int i = 1; i < s; ++i)          // L y = P b
-        for (int k = 0; k < i; ++k) b[i] -= A[i][k] * b[k];
-    for (int i = s - 1; i >= 0; --i) {   // U x = y
-        for (int k = i + 1; k < s; ++k) b[i] -= A[i][k] * b[k];
-        b[i] /= A[i][i];
-    }
-    double dot = 0.0;
-    for (int i = 0; i < s; ++i) {
-        w[(long)p * s + i] = b[i];
-        dot += b[i] * dk[(long)p * s + i];
-    }
-    unc[p] = llk[p] - dot;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -3545,13 +3191,12 @@ int launch_step(pnmol_filter* f, const double* Pin, const double* min, double fr
         Pin, f->Ppred, f->Kg, c, dp, min, f->mpred, f->shift, f->G, f->zbuf, mm, f->ctr, f->flags, f->nflags, f->p32);
     // K2: G = [S; P-H^T; z; I]  (STEADY: done by the previous step's k_readout launch)
     if (kind != STEP_STEADY) {
-        if (f->ellw > HW && f->sweep_mode != 0) {
-            // wide stencils (and sweep kernels that leave G alone): the rows of P- H^T first, S from them (k_front_s)
+        if (f->ellw > HW) {
+            // wide stencils: the rows of P- H^T first, S from them (k_front_s)
             k_front<<<dim3((mp + 255) / 256, (unsigned)Dp), 256, 0, st>>>(f->Ppred, f->G, f->rdiag, f->Rdense, mm, Dp, f->p32);
             k_front_s<<<dim3((mp + 255) / 256, (unsigned)mp), 256, 0, st>>>(f->G, f->rdiag, f->Rdense, mm);
         } else {
-            k_front<<<dim3((mp + 255) / 256, (unsigned)(Dp + mp + (f->sweep_mode == 0 ? mp : 0))), 256, 0, st>>>(
-                f->Ppred, f->G, f->rdiag, f->Rdense, mm, Dp, f->p32);  // (the per-panel path updates G in place: identity block too)
+            k_front<<<dim3((mp + 255) / 256, (unsigned)(Dp + mp)), 256, 0, st>>>(f->Ppred, f->G, f->rdiag, f->Rdense, mm, Dp, f->p32);
         }
     }
     const long rowI0 = (long)mp + Dp + NB;
@@ -3573,26 +3218,16 @@ int launch_step(pnmol_filter* f, const double* Pin, const double* min, double fr
             launch_sweep<N, true>(f->RT + pairs, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info, f->ctr, dd,
                                   f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home);
     } else {
-        if (f->sweep_mode == 1) {
-            // K3': the sweep alone as one dataflow launch
-            if (f->w_gemm) {
-                // rows of S, r^T, rows of Ls^-T through the sweep; W = (P- H^T) Ls^-T as a GEMM behind it
-                launch_sweep<N, false>(2 * f->CB + 1, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info, f->ctr, dd,
-                                       f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home, true);
-                const int nI = (int)(Dp / BDT), nt = nI * (mp / BDT);
-                k_w_gemm<<<8 * ((nt + 7) / 8), 256, 0, st>>>(f->G + (long)mp * mp, f->F + rowI0 * mp, f->F + (long)mp * mp, mp, nI, nt);
-            } else
-            launch_sweep<N, false>(f->RT, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info, f->ctr, dd,
-                                   f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home);
-        } else {
-            k_diag0<<<1, 128, 0, st>>>(f->G, f->F, f->Linv, mp, f->info, f->sdiag, f->ctr);
-            // K3: right-looking sweep, one launch per 32-column panel
-            for (int j = 0; j < f->CB; ++j) {
-                const int nrb = f->RT - (j + 1);
-                const int ncb = f->CB - 1 - j > 0 ? f->CB - 1 - j : 1;
-                k_panel<<<dim3(nrb, ncb), 256, 0, st>>>(f->G, f->F, f->Linv, mp, j, f->CB, f->RBS, f->info, f->sdiag, f->ctr);
-            }
-        }
+        // K3': the sweep alone as one dataflow launch
+        if (f->w_gemm) {
+            // rows of S, r^T, rows of Ls^-T through the sweep; W = (P- H^T) Ls^-T as a GEMM behind it
+            launch_sweep<N, false>(2 * f->CB + 1, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info, f->ctr, dd,
+                                   f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home, true);
+            const int nI = (int)(Dp / BDT), nt = nI * (mp / BDT);
+            k_w_gemm<<<8 * ((nt + 7) / 8), 256, 0, st>>>(f->G + (long)mp * mp, f->F + rowI0 * mp, f->F + (long)mp * mp, mp, nI, nt);
+        } else
+        launch_sweep<N, false>(f->RT, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info, f->ctr, dd,
+                               f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home);
         // K4: P = P- - W W^T (tiles) and, in extra blockIdx.y rows of the same launch, the vector ops
         const int tiles = dp / 16;
         const int vrows = (int)(((Dp + mp + 3) / 4 + tiles - 1) / tiles);
@@ -3741,22 +3376,6 @@ int prepare_graphs(pnmol_filter* f, pnmol_state* s, int k, double dt, hipGraphEx
     return rc;
 }
 
-// Covariance in the reference's state order (index j n + a, raw coordinates) as a (Dq x Dq) matrix padded with the
-// identity: input of the on-device Cholesky behind pnmol_state_get_cov_sqrtm.
-__global__ __launch_bounds__(256) void k_cov_reference_order(const void* __restrict__ P, double* __restrict__ Gc, int n,
-                                                             int d, int dp, long Dq, const double* __restrict__ sc, int p32) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= Dq * Dq) return;
-    const long r = e / Dq, c = e % Dq, D = (long)n * d, Dp = (long)n * dp;
-    double v = (r == c) ? 1.0 : 0.0;
-    if (r < D && c < D) {
-        const int j = (int)(r / n), a = (int)(r % n), k = (int)(c / n), b = (int)(c % n);
-        const long idx = ((long)a * dp + j) * Dp + (long)b * dp + k;
-        v = sc[a] * sc[b] * (p32 ? (double)static_cast<const float*>(P)[idx] : static_cast<const double*>(P)[idx]);
-    }
-    Gc[e] = v;
-}
-
 // Per-call results go to the host through a KERNEL that writes the mapped pinned staging buffer: one launch instead
 // of four hipMemcpyAsync calls (no SDMA queue, no runtime copy path inside the step loop).
 __global__ __launch_bounds__(256) void k_copy_out(const double* __restrict__ rec, const double* __restrict__ means,
@@ -3825,8 +3444,7 @@ int run_error_model_sweep(pnmol_filter* f, const MeasModel& mm) {
     hipStream_t st = f->ctx->stream;
     const int mp = f->mp;
     const long Dp = f->Dp;
-    k_front<<<dim3((mp + 255) / 256, (unsigned)(Dp + mp + (f->sweep_mode == 0 ? mp : 0))), 256, 0, st>>>(f->Qfull, f->G, f->rdiag,
-                                                                                                         f->Rdense, mm, Dp, f->p32);
+    k_front<<<dim3((mp + 255) / 256, (unsigned)(Dp + mp)), 256, 0, st>>>(f->Qfull, f->G, f->rdiag, f->Rdense, mm, Dp, f->p32);
     DowndateArgs dd{};
     launch_sweep<N, false>(f->RT, st, f->G, f->F, f->Linv, mp, f->CB, f->RT, f->flags, f->info_err, f->one, dd,
                            f->flags + f->RT + f->CB + 1, f->hs_scratch, f->p32 ? 2 : 0, f->xcd_home);
@@ -3933,86 +3551,6 @@ int sweep_info_result(pnmol_ctx* ctx, int inf, long limit, const char* who, cons
 
 extern "C" {
 
-// 2: pnmol_filter_desc.dtype, lifetime rule (refused destroys), pnmol_filter_sweep_layout; 3: pnmol_sqrt_filter_create takes dtype = 1
-int pnmol_abi_version(void) { return 3; }
-
-int pnmol_device_count(int* count) {
-    if (!count) return -1;
-    int c = 0;
-    if (hipGetDeviceCount(&c) != hipSuccess) {
-        *count = 0;
-        return -2;
-    }
-    *count = c;
-    return 0;
-}
-
-int pnmol_ctx_create(int device, pnmol_ctx** out) {
-    if (!out) return -1;
-    *out = nullptr;
-    int c = 0;
-    if (hipGetDeviceCount(&c) != hipSuccess || device < 0 || device >= c) return -2;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    pnmol_ctx* ctx = new pnmol_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ctx;
-        return -2;
-    }
-    *out = ctx;
-    return 0;
-}
-
-int pnmol_ctx_destroy(pnmol_ctx* ctx) {
-    if (!ctx) return -1;
-    if (ctx->children.load() != 0) {  // (lifetime rule, include/pnmol_hip.h: filters first)
-        ctx->err = "pnmol_ctx_destroy: " + std::to_string(ctx->children.load()) + " filter(s) of this ctx are still alive";
-        return -1;
-    }
-    hipSetDevice(ctx->device);
-    if (ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
-    return 0;
-}
-
-int pnmol_ctx_synchronize(pnmol_ctx* ctx) {
-    if (!ctx) return -1;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-const char* pnmol_last_error(pnmol_ctx* ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
-
-int pnmol_fd_solve_batched(pnmol_ctx* ctx, const double* gram_nss, const double* lk_ns, const double* llk_n, int N, int s,
-                           double* weights_ns, double* uncertainty_n) {
-    if (!ctx || !gram_nss || !lk_ns || !llk_n || !weights_ns || !uncertainty_n || N < 1 || s < 1 || s > FD_MAXS) {
-        if (ctx) ctx->err = "pnmol_fd_solve_batched: bad argument (need N >= 1, 1 <= s <= 16, non-null buffers)";
-        return -1;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    double* d = nullptr;
-    const size_t nG = (size_t)N * s * s, nV = (size_t)N * s;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (nG + 2 * nV + 2 * (size_t)N)));
-    double *dG = d, *dK = dG + nG, *dL = dK + nV, *dW = dL + N, *dU = dW + nV;
-    hipError_t e = hipMemcpyAsync(dG, gram_nss, sizeof(double) * nG, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dK, lk_ns, sizeof(double) * nV, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dL, llk_n, sizeof(double) * N, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        k_fd_solve<<<(unsigned)((N + 127) / 128), 128, 0, st>>>(dG, dK, dL, N, s, dW, dU);
-        e = hipMemcpyAsync(weights_ns, dW, sizeof(double) * nV, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(uncertainty_n, dU, sizeof(double) * N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipGetLastError();
-    (void)hipFree(d);
-    if (e != hipSuccess) {
-        ctx->err = std::string("pnmol_fd_solve_batched: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
-}
-
 int pnmol_cholesky_lower(pnmol_ctx* ctx, const double* A_nn, int n, double* L_nn) {
     if (!ctx || !A_nn || !L_nn || n < 1) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -4075,6 +3613,14 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
     if (desc->dtype != 0 && desc->dtype != 1) {
         ctx->err = "pnmol_filter_create: unknown dtype " + std::to_string(desc->dtype) + " (0 = fp64, 1 = fp32 covariance)";
         return -1;
+    }
+    int sweep_mode = 2;
+    if (const char* e = std::getenv("PNMOL_HIP_SWEEP")) {
+        sweep_mode = std::atoi(e);
+        if (sweep_mode != 1 && sweep_mode != 2) {
+            ctx->err = std::string("pnmol_filter_create: PNMOL_HIP_SWEEP=") + e + " (accepted: 1 = sweep, then down-date; 2 = fused)";
+            return -1;
+        }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pnmol_filter* f = new pnmol_filter();
@@ -4198,13 +3744,13 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
         FCHK(hipMemcpy(f->one, &h1, sizeof(int), hipMemcpyHostToDevice));
     }
     if (const char* gc = std::getenv("PNMOL_HIP_GRAPH_CHUNK")) f->graph_chunk = std::atoi(gc) / 2 * 2;
-    if (const char* e = std::getenv("PNMOL_HIP_SWEEP")) f->sweep_mode = std::atoi(e);
+    f->sweep_mode = sweep_mode;
     if (f->sweep_mode == 2 && n > 3) f->sweep_mode = 1;  // the fused down-date role is built for n <= 3
     {
         // Large fp64 problems (from D = 4096 with more column blocks than the register-resident sweep holds): the sweep
         // alone, then the SYRK of k_downdate_big -- measured on the 64x64 mesh against the fused launch (see k_downdate_big)
         const char* e = std::getenv("PNMOL_HIP_DD_BIG");
-        const bool fits = f->Dp % BDT == 0 && f->mp % BDK == 0 && f->sweep_mode >= 1 && (!f->p32 || f->sweep_mode == 2);
+        const bool fits = f->Dp % BDT == 0 && f->mp % BDK == 0 && (!f->p32 || f->sweep_mode == 2);
         const bool want = e ? std::atoi(e) != 0 : (f->Dp >= 8192 && f->CB > 17);
         if (fits && want) {
             f->dd_big = 1;
@@ -4218,7 +3764,7 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
         // PNMOL_HIP_SWEEP_XL forces it, the first such filter alive on its device gets the layout (pnmol_filter_sweep_layout
         // reports what was chosen, so that timings are attributable).
         static std::atomic<int> next_home[MAX_DEVICES];
-        const bool rl = sweep_rl_enabled() && f->CB <= 17 && f->sweep_mode >= 1;
+        const bool rl = sweep_rl_enabled() && f->CB <= 17;
         if (rl) {
             const int dv = ctx->device % MAX_DEVICES;
             const int others = live_rl_filters[dv].fetch_add(1);
@@ -4227,7 +3773,6 @@ int pnmol_filter_create(pnmol_ctx* ctx, const pnmol_filter_desc* desc, pnmol_fil
             f->xcd_home = xl ? next_home[dv].fetch_add(1) % 8 : -1;
         }
     }
-    FCHK(hipMalloc(&f->sdiag, sizeof(double) * (mp + 1)));
     // k_sweep: row[RT], diag[CB], abort, claim[CB*CB];  k_sweep_rl: rl_flags();  (the third term dates from the time when
     // pnmol_state_get_cov_sqrtm ran its square sweep on these words; it stays because the size is baked into captured graphs)
     f->nflags = std::max({f->RT + f->CB + 1 + f->CB * f->CB, rl_flags(f->RT, f->CB).total,
@@ -4315,7 +3860,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     if (f->ctr) hipFree(f->ctr);
     if (f->h_pin) hipHostFree(f->h_pin);
     void* ptrs[] = {f->ell_col, f->ell_val, f->Kg,   f->rdiag,   f->Rdense, f->shift,     f->G,        f->F,
-                    f->Linv,    f->Ppred,   f->mpred, f->zbuf,   f->var,    f->Sqinv,     f->rec,      f->part,  f->sdiag,
+                    f->Linv,    f->Ppred,   f->mpred, f->zbuf,   f->var,    f->Sqinv,     f->rec,      f->part,
                     f->info,    f->tmpP,    f->tmpMean, f->rec_means, f->rec_stds, f->flags, f->Qfull, f->one, f->info_err, f->hs_scratch, f->last_ctr, f->tickets};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -4348,7 +3893,7 @@ int pnmol_filter_dims(const pnmol_filter* f, int* d, int* n, int* m, int* dp, in
 
 int pnmol_filter_sweep_layout(const pnmol_filter* f, int* kernel, int* xcd_home) {
     if (!f) return -1;
-    if (kernel) *kernel = f->sweep_mode == 0 ? 0 : (sweep_rl_enabled() && f->CB <= 17 ? 2 : 1);
+    if (kernel) *kernel = sweep_rl_enabled() && f->CB <= 17 ? 2 : 1;
     if (xcd_home) *xcd_home = f->xcd_home;
     return 0;
 }
@@ -4483,274 +4028,6 @@ int pnmol_filter_predict_mean(pnmol_filter* f, const pnmol_state* in, double dt,
         }
         m_at_d[j] = s0 * acc;
     }
-    return 0;
-}
-
-int pnmol_state_create(pnmol_filter* f, pnmol_state** out) {
-    if (!f || !out) return -1;
-    *out = nullptr;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    pnmol_state* s = new pnmol_state();
-    s->f = f;
-    f->states.fetch_add(1);
-    const size_t Dp = (size_t)f->Dp;
-    if (hipMalloc(&s->mean, sizeof(double) * Dp) != hipSuccess || hipMalloc(&s->var, sizeof(double) * Dp) != hipSuccess ||
-        hipMalloc(&s->P, f->psz * Dp * Dp) != hipSuccess) {
-        ctx->err = "pnmol_state_create: hipMalloc failed";
-        pnmol_state_destroy(s);
-        return -4;
-    }
-    // (on the ctx stream, which is non-blocking: a memset on the null stream is not ordered against the kernels that write
-    // this state next, and with a second stream alive in the process it has been seen to land after them)
-    hipMemsetAsync(s->mean, 0, sizeof(double) * Dp, ctx->stream);
-    hipMemsetAsync(s->var, 0, sizeof(double) * Dp, ctx->stream);
-    hipMemsetAsync(s->P, 0, f->psz * Dp * Dp, ctx->stream);
-    *out = s;
-    return 0;
-}
-
-int pnmol_state_destroy(pnmol_state* s) {
-    if (!s) return -1;
-    if (s->f->pending_state == s) {
-        s->f->ctx->err = "pnmol_state_destroy: this state is the target of an unfinished pnmol_filter_steps_begin";
-        return -1;
-    }
-    if (pnmol_record_holds(s)) {
-        s->f->ctx->err = "pnmol_state_destroy: this state is a slot of the recorder its filter has set (clear the recorder first)";
-        return -1;
-    }
-    s->f->states.fetch_sub(1);
-    hipSetDevice(s->f->ctx->device);
-    if (s->mean) hipFree(s->mean);
-    if (s->var) hipFree(s->var);
-    if (s->P) hipFree(s->P);
-    delete s;
-    return 0;
-}
-
-int pnmol_state_clone(const pnmol_state* s, pnmol_state** out) {
-    if (!s || !out) return -1;
-    int rc = pnmol_state_create(s->f, out);
-    if (rc != 0) return rc;
-    pnmol_ctx* ctx = s->f->ctx;
-    pnmol_state* o = *out;
-    const size_t Dp = (size_t)s->f->Dp;
-    HIPCHK(ctx, hipMemcpyAsync(o->mean, s->mean, sizeof(double) * Dp, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(o->var, s->var, sizeof(double) * Dp, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(o->P, s->P, s->f->psz * Dp * Dp, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    o->t = s->t, o->frame_dt = s->frame_dt;
-    return 0;
-}
-
-int pnmol_state_set(pnmol_state* s, double t, const double* mean_nd, const double* cov_DD) {
-    if (!s || !mean_nd || !cov_DD) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = f->n, d = f->ds, dp = f->dp;
-    const long D = (long)n * d, Dp = f->Dp;
-    std::vector<double> hm((size_t)Dp, 0.0), hv((size_t)Dp, 0.0), hP((size_t)Dp * Dp, 0.0);
-    for (int a = 0; a < n; ++a)
-        for (int j = 0; j < d; ++j) {
-            hm[(size_t)a * dp + j] = mean_nd[(size_t)a * d + j];
-            hv[(size_t)a * dp + j] = cov_DD[((size_t)j * n + a) * D + (size_t)j * n + a];
-        }
-    for (int a = 0; a < n; ++a)
-        for (int j = 0; j < d; ++j) {
-            const double* src = cov_DD + ((size_t)j * n + a) * D;
-            double* dst = &hP[((size_t)a * dp + j) * Dp];
-            for (int b = 0; b < n; ++b)
-                for (int k = 0; k < d; ++k) dst[(size_t)b * dp + k] = src[(size_t)k * n + b];
-        }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(s->mean, hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(s->var, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice));
-    if (f->p32) {
-        std::vector<float> hPf(hP.begin(), hP.end());
-        HIPCHK(ctx, hipMemcpy(s->P, hPf.data(), sizeof(float) * hPf.size(), hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(ctx, hipMemcpy(s->P, hP.data(), sizeof(double) * hP.size(), hipMemcpyHostToDevice));
-    }
-    s->t = t;
-    s->frame_dt = 0.0;
-    return 0;
-}
-
-namespace {
-// P = C C^T written straight into the state's derivative-major padded layout, C (D x D, any square root) in the
-// reference's F-flattened order: P[(a dp + j)(Dp) + (b dp + k)] = sum_c C[j n + a][c] C[k n + b][c].  One 32x32 tile of
-// points (j, k) for one derivative pair (a, b) per block, on the MFMA; also the marginal variances.
-__global__ __launch_bounds__(256) void k_cct_layout(void* __restrict__ P, double* __restrict__ var,
-                                                    const double* __restrict__ C, int d, int n, int dp, long Dp, int p32) {
-    __shared__ double sA[32][33], sB[32][33];
-    const int t = threadIdx.x, w = t >> 6, lane = t & 63, fr = lane & 15, fk = lane >> 4, wr = w >> 1, wc = w & 1;
-    const int tx = t & 31, ty = t >> 5;
-    const int a = blockIdx.z / n, b = blockIdx.z % n, j0 = blockIdx.y * 32, k0 = blockIdx.x * 32;
-    const long D = (long)n * d;
-    d4 acc = {0, 0, 0, 0};
-    for (long c0 = 0; c0 < D; c0 += 32) {
-        for (int r = ty; r < 32; r += 8) {
-            const int j = j0 + r, k = k0 + r;
-            const long c = c0 + tx;
-            sA[r][tx] = (j < d && c < D) ? C[((long)j * n + a) * D + c] : 0.0;
-            sB[r][tx] = (k < d && c < D) ? C[((long)k * n + b) * D + c] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int st = 0; st < 8; ++st)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sA[wr * 16 + fr][4 * st + fk], sB[wc * 16 + fr][4 * st + fk], acc, 0, 0, 0);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int j = j0 + wr * 16 + fk + 4 * r, k = k0 + wc * 16 + fr;
-        if (j < d && k < d) {
-            const long idx = ((long)a * dp + j) * Dp + (long)b * dp + k;
-            if (p32) static_cast<float*>(P)[idx] = (float)acc[r];
-            else static_cast<double*>(P)[idx] = acc[r];
-            if (a == b && j == k) var[(long)a * dp + j] = acc[r];
-        }
-    }
-}
-}  // namespace
-
-int pnmol_state_set_sqrtm(pnmol_state* s, double t, const double* mean_nd, const double* cov_sqrtm_DD) {
-    if (!s || !mean_nd || !cov_sqrtm_DD) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = f->n, d = f->ds, dp = f->dp;
-    const long D = (long)n * d, Dp = f->Dp;
-    std::vector<double> hm((size_t)Dp, 0.0);
-    for (int a = 0; a < n; ++a)
-        for (int j = 0; j < d; ++j) hm[(size_t)a * dp + j] = mean_nd[(size_t)a * d + j];
-    double* dC = nullptr;
-    if (hipMalloc(&dC, sizeof(double) * (size_t)D * D) != hipSuccess) return -4;
-    int rc = 0;
-    do {
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = -2; break; }
-        if (hipMemcpy(s->mean, hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice) != hipSuccess) { rc = -2; break; }
-        if (hipMemcpy(dC, cov_sqrtm_DD, sizeof(double) * (size_t)D * D, hipMemcpyHostToDevice) != hipSuccess) { rc = -2; break; }
-        if (hipMemsetAsync(s->P, 0, f->psz * (size_t)Dp * Dp, ctx->stream) != hipSuccess) { rc = -2; break; }
-        if (hipMemsetAsync(s->var, 0, sizeof(double) * (size_t)Dp, ctx->stream) != hipSuccess) { rc = -2; break; }
-        hipLaunchKernelGGL(k_cct_layout, dim3((d + 31) / 32, (d + 31) / 32, n * n), dim3(256), 0, ctx->stream, (void*)s->P, s->var,
-                           dC, d, n, dp, Dp, f->p32);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = -2; break; }
-    } while (0);
-    hipFree(dC);
-    if (rc) {
-        ctx->err = std::string("pnmol_state_set_sqrtm: ") + hipGetErrorString(hipGetLastError());
-        return rc;
-    }
-    s->t = t;
-    s->frame_dt = 0.0;
-    return 0;
-}
-
-int pnmol_state_get_time(const pnmol_state* s, double* t) {
-    if (!s || !t) return -1;
-    *t = s->t;
-    return 0;
-}
-
-int pnmol_state_get_mean(const pnmol_state* s, double* mean_nd) {
-    if (!s || !mean_nd) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<double> hm((size_t)f->Dp);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(hm.data(), s->mean, sizeof(double) * hm.size(), hipMemcpyDeviceToHost));
-    double sc[MAXN];
-    frame_scales(s, sc);
-    for (int a = 0; a < f->n; ++a)
-        for (int j = 0; j < f->ds; ++j) mean_nd[(size_t)a * f->ds + j] = sc[a] * hm[(size_t)a * f->dp + j];
-    return 0;
-}
-
-int pnmol_state_get_cov_sqrtm(const pnmol_state* s, double* C_DD) {
-    if (!s || !C_DD) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int n = f->n, d = f->ds;
-    const long D = (long)n * d;
-    const int Dq = round_up((int)D, NB), cb = Dq / NB;
-    SweepWs ws;
-    double* dsc = nullptr;
-    hipError_t e = sweep_ws_alloc(&ws, ctx, cb, cb);
-    if (e == hipSuccess) e = hipMalloc(&dsc, sizeof(double) * MAXN);
-    int rc = 0, inf = 0;
-    std::vector<double> hF;
-    if (e == hipSuccess) {
-        double sc[MAXN];
-        frame_scales(s, sc);
-        e = hipMemcpy(dsc, sc, sizeof(double) * MAXN, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            k_cov_reference_order<<<(unsigned)(((long)Dq * Dq + 255) / 256), 256, 0, st>>>(s->P, ws.G, n, d, f->dp, Dq, dsc, f->p32);
-            rc = sweep_ws_enqueue(f, ws, st, 1, "pnmol_state_get_cov_sqrtm");  // (lenient: a covariance may be singular)
-            hF.resize((size_t)Dq * Dq);
-            if (rc == 0) e = hipMemcpyAsync(hF.data(), ws.F, sizeof(double) * hF.size(), hipMemcpyDeviceToHost, st);
-            if (rc == 0 && e == hipSuccess) e = hipMemcpyAsync(&inf, ws.info, sizeof(int), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-    }
-    sweep_ws_free(&ws);
-    if (dsc) (void)hipFree(dsc);
-    if (rc != 0) return rc;
-    if (e != hipSuccess) {
-        ctx->err = std::string("pnmol_state_get_cov_sqrtm: ") + hipGetErrorString(e);
-        return -2;
-    }
-    if ((rc = sweep_info_result(ctx, inf, Dq, "pnmol_state_get_cov_sqrtm", "covariance not positive semi-definite")) != 0) return rc;
-    for (long r = 0; r < D; ++r) std::memcpy(C_DD + r * D, &hF[(size_t)r * Dq], sizeof(double) * D);
-    return 0;
-}
-
-int pnmol_state_get_marginal_var(const pnmol_state* s, double* var_nd) {
-    if (!s || !var_nd) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<double> hv((size_t)f->Dp);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(hv.data(), s->var, sizeof(double) * hv.size(), hipMemcpyDeviceToHost));
-    double sc[MAXN];
-    frame_scales(s, sc);
-    for (int a = 0; a < f->n; ++a)
-        for (int j = 0; j < f->ds; ++j) var_nd[(size_t)a * f->ds + j] = sc[a] * sc[a] * hv[(size_t)a * f->dp + j];
-    return 0;
-}
-
-int pnmol_state_get_cov(const pnmol_state* s, double* cov_DD) {
-    if (!s || !cov_DD) return -1;
-    pnmol_filter* f = s->f;
-    pnmol_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = f->n, d = f->ds, dp = f->dp;
-    const long D = (long)n * d, Dp = f->Dp;
-    std::vector<double> hP((size_t)Dp * Dp);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (f->p32) {
-        std::vector<float> hPf(hP.size());
-        HIPCHK(ctx, hipMemcpy(hPf.data(), s->P, sizeof(float) * hPf.size(), hipMemcpyDeviceToHost));
-        std::copy(hPf.begin(), hPf.end(), hP.begin());
-    } else {
-        HIPCHK(ctx, hipMemcpy(hP.data(), s->P, sizeof(double) * hP.size(), hipMemcpyDeviceToHost));
-    }
-    double sc[MAXN];
-    frame_scales(s, sc);
-    for (int a = 0; a < n; ++a)
-        for (int j = 0; j < d; ++j) {
-            double* dst = cov_DD + ((size_t)j * n + a) * D;
-            const double* src = &hP[((size_t)a * dp + j) * Dp];
-            for (int b = 0; b < n; ++b)
-                for (int k = 0; k < d; ++k) dst[(size_t)k * n + b] = sc[a] * sc[b] * src[(size_t)b * dp + k];
-        }
     return 0;
 }
 

@@ -107,7 +107,7 @@ struct pnmol_filter {
     int w_gemm = 0;        // ... and W = (P- H^T) Ls^-T as a GEMM behind a sweep without the rows of W (k_w_gemm)
     int dd_big = 0;        // large problems: sweep alone + k_downdate_big (PNMOL_HIP_DD_BIG=0/1 overrides; see there)
     int sweep_mode = 2;    // PNMOL_HIP_SWEEP: 2 = k_sweep with the covariance down-date riding along in the same launch,
-                           // 1 = k_sweep, then k_downdate; 0 = k_diag0 + one k_panel launch per panel, then k_downdate
+                           // 1 = k_sweep, then k_downdate (any other value: pnmol_filter_create refuses)
     int ds = 0;  // spatial components of the state (= d, or 2d for the latent-force model [u; eps])
     bool counted = false;  // this filter is in live_rl_filters[device]
     bool registered = false;  // this filter is counted in ctx->children
@@ -131,7 +131,7 @@ struct pnmol_filter {
     hipEvent_t ev_op = nullptr;
     double *Kg = nullptr, *rdiag = nullptr, *Rdense = nullptr, *shift = nullptr;
     double *G = nullptr, *F = nullptr, *Linv = nullptr, *Ppred = nullptr, *mpred = nullptr, *zbuf = nullptr;
-    double *var = nullptr, *Sqinv = nullptr, *rec = nullptr, *part = nullptr, *sdiag = nullptr;
+    double *var = nullptr, *Sqinv = nullptr, *rec = nullptr, *part = nullptr;
     int* info = nullptr;
     std::vector<double> sqdiag;
     double* Qfull = nullptr;  // Q1 (x) K as a dense Dp x Dp matrix (on-device error model), allocated on first use

@@ -354,7 +354,7 @@ class Filter:
         """(kernel, xcd_home) of this filter's sweep launch: `pnmol_filter_sweep_layout`."""
         k, x = ctypes.c_int(0), ctypes.c_int(0)
         self.lib.pnmol_filter_sweep_layout(self.handle, ctypes.byref(k), ctypes.byref(x))
-        return {"kernel": ("per_panel", "k_sweep", "k_sweep_rl")[k.value], "xcd_home": x.value}
+        return {"kernel": {1: "k_sweep", 2: "k_sweep_rl"}[k.value], "xcd_home": x.value}
 
     def dims(self):
         v = [ctypes.c_int(0) for _ in range(5)]

@@ -7,6 +7,7 @@ No reference counterpart (the reference has no FFI): this 
 
 import ctypes
 import gc
+import os
 
 import numpy as np
 import pytest
@@ -96,3 +97,35 @@ def test_python_mirror_frees_states_whatever_the_finalisation_order(hip_ctx):
     assert flt2.handle is None and not flt2._live
     st._destroy()                # finds its entry gone: must not touch the library
     assert st.handle is None
+
+
+def test_unknown_sweep_switch_is_refused_before_anything_is_counted():
+    """PNMOL_HIP_SWEEP takes 1 or 2.  Any other value (0 was the per-panel sweep, removed) makes pnmol_filter_create fail with a
+    message that names the variable, before the filter is counted in the ctx: the same ctx then serves a filter and a step,
+    and can be destroyed.  N = 8 mesh points, nu = 2."""
+    lib = _hip.load_library()
+    ctx = _hip.Context(0)            # a ctx of its own (not the cached one): it is destroyed below
+    desc, keep = _desc(d=8, nu=2)
+    L, B, E, R, G = keep
+    old = os.environ.get("PNMOL_HIP_SWEEP")
+    try:
+        for bad in ("0", "3"):
+            os.environ["PNMOL_HIP_SWEEP"] = bad          # read when the filter is created
+            with pytest.raises(_hip.PnmolHipError, match="PNMOL_HIP_SWEEP"):
+                _hip.Filter(ctx, L=L, B=B, E_sqrtm=E, R_sqrtm=R, Gamma=G, num_derivatives=2)
+    finally:
+        if old is None:
+            del os.environ["PNMOL_HIP_SWEEP"]
+        else:
+            os.environ["PNMOL_HIP_SWEEP"] = old
+    flt = _hip.Filter(ctx, L=L, B=B, E_sqrtm=E, R_sqrtm=R, Gamma=G, num_derivatives=2)
+    s_in, s_out, info = flt.new_state(), flt.new_state(), _hip.StepOut()
+    s_in.set(0.0, np.ones((3, 8)), np.eye(24))
+    assert lib.pnmol_filter_step(flt.handle, s_in.handle, 2.0 ** -7, s_out.handle, ctypes.byref(info), None) == 0
+    t = ctypes.c_double(-1.0)
+    assert lib.pnmol_state_get_time(s_out.handle, ctypes.byref(t)) == 0 and t.value == 2.0 ** -7
+    s_in._destroy(), s_out._destroy()
+    flt.__del__()
+    assert flt.handle is None
+    assert lib.pnmol_ctx_destroy(ctx.handle) == 0        # the refusals left nothing counted in ctx->children
+    ctx.handle = None

@@ -1,4 +1,5 @@
-// Standalone timing of k_downdate<3> (N=512 sizes) for several chunk ranges.  Build: tools/README.md (as potrf_bench.hip).
+// Standalone timing of k_downdate<3> (N=512 sizes) for several chunk ranges.  Build: tools/README.md (this file includes
+// csrc/pnmol_hip.hip; the other csrc/*.hip go on the command line).
 #include "../pnmol-experiments_amd/csrc/pnmol_hip.hip"
 #include <random>
 int main() {
