@@ -29,7 +29,8 @@
  *     backwards-compatible additions, nothing existing changed.  So was the dense output (`pnmol_state_predict*`,
  *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`) and the measurement
  *     update (`pnmol_state_observe`), the recorder of the constant-step loop (`pnmol_filter_set_recorder`, `_recorder_pending`,
- *     `_recorder_means`) and the one-call backward pass (`pnmol_smoother_steps`).
+ *     `_recorder_means`), the one-call backward pass (`pnmol_smoother_steps`) and the linearisation points of the loop
+ *     (`pnmol_filter_set_linearization_points`, `_linearization_pending`, `pnmol_filter_linearize_at`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -219,6 +220,29 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
  * diagonal entry.  The uncertainty of the finite-difference weights of G is not modelled (the error model keeps that of L). */
 typedef struct pnmol_convection { int deg_c; double c[PNMOL_REACTION_MAXDEG + 1]; pnmol_reaction r; } pnmol_convection;
 int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, const double* G_dd);   /* NULL term clears */
+
+/* Linearisation points for the constant-step loop (iterated smoother) --------------------------------------------------------
+ * `evaluate_ode` (white.py:192-208) linearises f at m_at = E0 m^-, the step's own predicted mean.  An iterated extended Kalman
+ * smoother repeats the forward pass with every step linearised at the previous pass's SMOOTHED mean instead; no reference
+ * counterpart.  `pnmol_filter_set_linearization_points(f, count, u_cd)`: u_cd is (count, d) row-major, derivative 0 of the PDE
+ * state in raw coordinates; the table is copied to the device and the cursor goes to row 0.  While a table is set, the i-th step
+ * `pnmol_filter_steps(_begin)` takes since then linearises the term at row i in place of the predicted value (for a convection
+ * term the row's stencil neighbours come from the same row of the table); the arithmetic behind the point, and the rest of the
+ * step, are unchanged.  Rows are consumed across calls (a schedule's runt last step is a call of its own); a call that fails
+ * (-2 / -3) consumes none, `pnmol_filter_prepare_steps` consumes none.  The row is addressed on the device (a cursor word written
+ * once per call plus the loop's step counter), so the captured graphs of the loop serve any position; graphs captured without a
+ * table are not replayed with one, nor the reverse.  Composes with the recorder and the sensor plan in one call; the order per
+ * step is linearise, step, observation update, record.  count = 0 or a NULL table clears; so does every term setter (a NULL
+ * term included).  `pnmol_filter_linearize` and `pnmol_filter_step` are unchanged and consume no row.
+ * -1 (reason in `pnmol_last_error`, nothing enqueued): null filter, no term set, count < 0, an entry that is not finite, called
+ * between `pnmol_filter_steps_begin` and `_end`; and from `pnmol_filter_steps(_begin)`: more steps asked for than rows left.
+ * `pnmol_filter_linearization_pending`: the cursor (the row the next step takes) and the number of rows (0, 0: no table).
+ * `pnmol_filter_linearize_at(f, u_d)`: the host-callable counterpart of `pnmol_filter_linearize` -- d numbers go up and the same
+ * kernels linearise the term there (no synchronisation; the error model is forgotten); `pnmol_filter_step` follows.  A loop over a
+ * table gives the bits of this call in front of every single step.  -1: null argument, no term set. */
+int pnmol_filter_set_linearization_points(pnmol_filter* f, int count, const double* u_cd);
+int pnmol_filter_linearization_pending(const pnmol_filter* f, int* next, int* count);
+int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d);
 
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);

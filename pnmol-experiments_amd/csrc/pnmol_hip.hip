@@ -3277,12 +3277,13 @@ int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double 
 }
 
 // a step of the constant-step loop: with a reaction set the operator is re-linearised at this step's predicted mean first
-// (k_linearize, pnmol_reaction.hip); with a recorder set the state behind the step goes into its slot (k_record, pnmol_record.hip;
-// keep = false: a sensor update follows at once and the caller records behind it)
+// (k_linearize, pnmol_reaction.hip; with a table of linearisation points set: at the table's row for this step); with a
+// recorder set the state behind the step goes into its slot (k_record, pnmol_record.hip; keep = false: a sensor update follows
+// at once and the caller records behind it)
 int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
               double* varout, StepKind kind, bool keep = true) {
     if (has_term(f)) {
-        if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt)) return rc;
+        if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt, true)) return rc;
     }
     if (int rc = dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind)) return rc;
     return keep ? pnmol_record_enqueue(f, Pout, mout, varout) : 0;
@@ -4079,6 +4080,9 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     // a recorder: enough slots left and s not among them -- or the refusal, before anything is enqueued
     int rc = pnmol_record_begin(f, s, k);
     if (rc != 0) return rc;
+    // a table of linearisation points: enough rows left -- or the refusal, before anything is enqueued
+    rc = pnmol_linearize_begin(f, k);
+    if (rc != 0) return rc;
     // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
     std::vector<int> ob_entry;
     rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
@@ -4094,6 +4098,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
     if ((rc = pnmol_record_enqueue_cursor(f)) != 0) return rc;
+    if ((rc = pnmol_linearize_enqueue_cursor(f)) != 0) return rc;
     if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
@@ -4210,6 +4215,8 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
     // in time, so a step's own error at or before j takes precedence.
     int ob_step = -1;
     const int ob_rc = pnmol_observe_plan_collect(f, &ob_step);
+    // a table of linearisation points: the call's rows are consumed, unless it failed (the cursor then stays where the call began)
+    pnmol_linearize_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);
     if (ob_rc != 0) {
         const int first = stuck >= 0 && (bad < 0 || stuck < bad) ? stuck : bad;  // the first step that failed by itself
         if (first < 0 || first > ob_step) return ob_rc;                         // (ctx->err names entry, pivot and step)
@@ -4251,9 +4258,11 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
     if (e == hipSuccess) {
         const int ob_next = pnmol_observe_plan_cursor(f);  // (a sensor plan: the rehearsal applies entries; the cursor goes back)
         const int rec_next = pnmol_record_cursor(f);       // (a recorder: the rehearsal fills slots the real call fills again)
+        const int lin_next = pnmol_linearize_cursor(f);    // (linearisation points: the rehearsal consumes rows of the real call)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
         pnmol_observe_plan_rewind(f, ob_next);
         pnmol_record_rewind(f, rec_next);
+        pnmol_linearize_rewind(f, lin_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

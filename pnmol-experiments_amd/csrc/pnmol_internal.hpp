@@ -209,6 +209,9 @@ struct pnmol_filter {
     // reaction leave it alone); a convection term rebuilds it with every set call (G comes with the term), and so does a system set
     // after a convection term -- one more cold setter call than when each kind kept an image of its own.
     TermImage term_img;
+    // Linearisation points of the constant-step loop (pnmol_filter_set_linearization_points, pnmol_reaction.hip): NULL = none, every
+    // step is linearised at its own predicted mean.  While a table is set the i-th step taken since is linearised at its row i.
+    struct LinearizeDev* lin_plan = nullptr;
 };
 inline bool has_term(const pnmol_filter* f) { return f->term != TermKind::none; }
 
@@ -326,8 +329,19 @@ void pnmol_reaction_free_ws(pnmol_filter* f);
 // pnmol_reaction.hip: enqueue k_linearize (k_linearize_system for a coupled system, k_linearize_convection for a convection
 // term) on the ctx stream for one step over dt from the mean `mean` (Dp, in the frame frame_dt; 0 = raw coordinates): the
 // diagonal (same-point; for a convection term all) slots of ell_val and the shift become those of the EK1 linearisation of the
-// term at the predicted mean.  Needs has_term(f); no synchronisation.  -2: the launch failed.
-int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt);
+// term at the predicted mean -- or, for a step of the loop (loop_step) while a table of linearisation points is set, at the row
+// the device words name (the cursor word of the running call plus the loop's step counter; outside the loop those words name
+// nothing, so pnmol_filter_linearize passes false).  Needs has_term(f); no synchronisation.  -2: the launch failed.
+int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt, bool loop_step);
+// pnmol_reaction.hip: the table of linearisation points inside pnmol_filter_steps_begin / _end, as the recorder's functions above:
+// the refusal of a call of k steps (-1, ctx->err set; nothing of HIP is touched), the cursor words of the running call on the ctx
+// stream (once per call, in front of its steps), behind the call's synchronisation the cursor moves (ok) or stays (the call
+// failed), and the cursor and putting it back for a rehearsal.
+int pnmol_linearize_begin(pnmol_filter* f, int k);
+int pnmol_linearize_enqueue_cursor(pnmol_filter* f);
+void pnmol_linearize_collect(pnmol_filter* f, int k, bool ok);
+int pnmol_linearize_cursor(const pnmol_filter* f);
+void pnmol_linearize_rewind(pnmol_filter* f, int next);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);
 // pnmol_hip.hip: make ell_col / ell_val at least w slots wide.  Growing frees them (ellw = 0 until the caller has filled them): the

@@ -19,13 +19,28 @@
 //
 // The three kinds share the predicted value and the rational evaluation on the device, and one image (pnmol_term_image.hpp), one
 // capability check and one installer (install_term) on the host; a filter holds one term (pnmol_filter::term).
+//
+// Linearisation points (`pnmol_filter_set_linearization_points`, `pnmol_filter_linearize_at`): an iterated smoother repeats the
+// forward pass with every step linearised at the previous pass's smoothed mean.  The three kernels take their point from one
+// helper (point_value): the predicted value as above, or the entry of a row of a device-resident table, which the launch finds
+// from two device words and the loop's step counter (point_row) -- identical arguments at every step, as the recorder's k_record.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "pnmol_internal.hpp"
+#include "pnmol_linearize_plan.hpp"
 #include "pnmol_term_image.hpp"
+
+// The table of linearisation points of the constant-step loop (pnmol_filter_set_linearization_points): host logic in
+// pnmol_linearize_plan.hpp; the rows and the two words the kernels address them by live on the device, as the recorder's slots do.
+struct LinearizeDev {
+    LinearizePlan plan;
+    double* table = nullptr;  // device: cap rows of d
+    int* words = nullptr;     // device: [plan.next of the running call, plan.count], written once per call (k_linearize_cursor)
+    int cap = 0;
+};
 
 namespace {
 
@@ -34,10 +49,22 @@ struct Frame {
     double c[MAXN];  // A1[0][a] * ts[a]: row 0 of the transition times the frame change of the input mean
     double s0;       // raw-coordinate scale of derivative 0 in the frame of dt
 };
+// where a launch takes its linearisation point from.  u == nullptr: the step's own predicted mean.  Otherwise rows of d numbers
+// (derivative 0, raw coordinates): with words, row words[0] + *ctr of words[1] -- the cursor of the running call plus the loop's step
+// counter, which k_predict moves only behind this launch, so the step that takes *ctr to j + 1 is linearised at row cursor + j and
+// every step launches with identical arguments (the captured graphs of the loop replay at any position); without words, row 0
+// (pnmol_filter_linearize_at).
+struct PointSource {
+    const double* u;
+    const int* words;
+    const int* ctr;
+    int d;
+};
 template <class Descriptor>
 struct LinearizeArgs {
     Descriptor t;
     Frame fr;
+    PointSource pt;
 };
 
 // derivative 0 of the predicted mean at state component j, in raw coordinates: the arithmetic of pnmol_filter_predict_mean
@@ -46,6 +73,26 @@ __device__ __forceinline__ double predicted_value(const Frame& fr, int n, const 
     double acc = 0.0;
     for (int q = 0; q < n; ++q) acc = acc + fr.c[q] * mean[(long)q * dp + j];
     return fr.s0 * acc;
+}
+
+// The row of this launch (nullptr: the predicted mean).  false: an index outside the table -- the launch reads and writes nothing
+// (the host refuses such calls before they are enqueued; this is the bound of the table all the same).
+__device__ __forceinline__ bool point_row(const PointSource& pt, const double*& row) {
+    row = nullptr;
+    if (!pt.u) return true;
+    int r = 0;
+    if (pt.words) {
+        r = pt.words[0] + *pt.ctr;
+        if (r < 0 || r >= pt.words[1]) return false;
+    }
+    row = pt.u + (long)r * pt.d;
+    return true;
+}
+
+// the point a term is linearised at, component j: the table's entry, or the predicted value with its arithmetic untouched
+__device__ __forceinline__ double point_value(const Frame& fr, int n, const double* __restrict__ mean, int dp, int j,
+                                              const double* __restrict__ row) {
+    return row ? row[j] : predicted_value(fr, n, mean, dp, j);
 }
 
 // value and derivative of a polynomial (ascending coefficients, degree deg; deg < 0: absent, both zero), by Horner
@@ -83,11 +130,13 @@ __global__ __launch_bounds__(256) void k_linearize(LinearizeArgs<pnmol_reaction>
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= mp) return;
+    const double* row;
+    if (!point_row(a.pt, row)) return;
     if (i >= d) {
         shift[i] = 0.0;
         return;
     }
-    const double u = predicted_value(a.fr, n, mean, dp, i);
+    const double u = point_value(a.fr, n, mean, dp, i, row);
     double r, dr;
     eval_reaction(a.t, u, r, dr);
     const long e = (long)slot[i] * mp + i;
@@ -149,6 +198,8 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeArgs<pnmol_re
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= mp) return;
+    const double* row;
+    if (!point_row(a.pt, row)) return;
     if (i >= d) {
         shift[i] = 0.0;
         return;
@@ -157,7 +208,7 @@ __global__ __launch_bounds__(256) void k_linearize_system(LinearizeArgs<pnmol_re
     const int c = i / N, j = i - c * N;
     double u[SC];
 #pragma unroll
-    for (int k = 0; k < SC; ++k) u[k] = k < C ? predicted_value(a.fr, n, mean, dp, k * N + j) : 0.0;
+    for (int k = 0; k < SC; ++k) u[k] = k < C ? point_value(a.fr, n, mean, dp, k * N + j, row) : 0.0;
     double r = 0.0, J[SC];
 #pragma unroll
     for (int k = 0; k < SC; ++k) J[k] = 0.0;
@@ -207,11 +258,13 @@ __global__ __launch_bounds__(256) void k_linearize_convection(LinearizeArgs<pnmo
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= mp) return;
+    const double* row;
+    if (!point_row(a.pt, row)) return;
     if (i >= d) {
         shift[i] = 0.0;
         return;
     }
-    const double u = predicted_value(a.fr, n, mean, dp, i);
+    const double u = point_value(a.fr, n, mean, dp, i, row);
     double g = 0.0;
     bool first = true;
     for (int e = 0; e < w; ++e) {
@@ -219,7 +272,7 @@ __global__ __launch_bounds__(256) void k_linearize_convection(LinearizeArgs<pnmo
         if (col < 0) break;
         const double gv = img_g[(long)e * mp + i];
         if (gv == 0.0) continue;
-        const double prod = gv * predicted_value(a.fr, n, mean, dp, col);
+        const double prod = gv * point_value(a.fr, n, mean, dp, col, row);
         g = first ? prod : g + prod;
         first = false;
     }
@@ -317,6 +370,16 @@ void free_term_image(pnmol_filter* f) {
     im = TermImage{};
 }
 
+// (the caller knows the stream idle or the table out of use, and has dropped the graphs that address it)
+void free_linearize_table(pnmol_filter* f) {
+    LinearizeDev* l = f->lin_plan;
+    if (!l) return;
+    for (void* q : {(void*)l->table, (void*)l->words})
+        if (q) (void)hipFree(q);
+    delete l;
+    f->lin_plan = nullptr;
+}
+
 template <class T>
 int upload(pnmol_ctx* ctx, T** dst, const std::vector<T>& src) {
     if (src.empty()) return 0;
@@ -371,8 +434,13 @@ int put_term_image(pnmol_filter* f, TermKind kind, int ncomp, const double* G) {
 // Make `kind` (none: clear) the filter's term; its descriptor is in place.  The descriptor travels by value in the captured
 // launches, width and pointers are baked in too, and the loop's launch sequence differs with and without a term: the graphs go.
 // A failure leaves no half-installed term: no image, no term, the operator given at creation.
+// A table of linearisation points belongs to the term it was set for: it goes with it.
 int install_term(pnmol_filter* f, TermKind kind, int ncomp = 0, const double* G = nullptr) {
     pnmol_drop_graphs(f);
+    if (f->lin_plan) {
+        HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (a launch that reads the table may still be in flight)
+        free_linearize_table(f);
+    }
     const bool image = kind == TermKind::system || kind == TermKind::convection;
     const int rc = image ? put_term_image(f, kind, ncomp, G) : pnmol_ell_restore_base(f, true);
     f->sq_dt = -1.0;  // the error model belongs to the operator that was set
@@ -386,11 +454,9 @@ int install_term(pnmol_filter* f, TermKind kind, int ncomp = 0, const double* G 
     return rc;
 }
 
-}  // namespace
-
-void pnmol_reaction_free_ws(pnmol_filter* f) { free_term_image(f); }
-
-int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt) {
+// k_linearize (k_linearize_system, k_linearize_convection) on the ctx stream for one step over dt from `mean` (in the frame
+// frame_dt), the point taken from `pt`
+int enqueue_linearize(pnmol_filter* f, const double* mean, double frame_dt, double dt, const PointSource& pt) {
     Frame fr;
     for (int q = 0; q < MAXN; ++q) fr.c[q] = 0.0;
     for (int q = 0; q < f->n; ++q) {
@@ -404,15 +470,15 @@ int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt,
     switch (f->term) {
         case TermKind::none: return -1;
         case TermKind::scalar:
-            k_linearize<<<blocks, 256, 0, st>>>({f->reaction, fr}, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot,
+            k_linearize<<<blocks, 256, 0, st>>>({f->reaction, fr, pt}, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot,
                                                 f->shift, f->d, f->dp, f->mp);
             break;
         case TermKind::system:
-            k_linearize_system<<<blocks, 256, 0, st>>>({f->sys, fr}, f->n, f->d / f->sys.ncomp, mean, f->ell_val, im.val, im.slot,
+            k_linearize_system<<<blocks, 256, 0, st>>>({f->sys, fr, pt}, f->n, f->d / f->sys.ncomp, mean, f->ell_val, im.val, im.slot,
                                                        f->shift, f->d, f->dp, f->mp);
             break;
         case TermKind::convection:
-            k_linearize_convection<<<blocks, 256, 0, st>>>({f->cv, fr}, f->n, im.w, mean, f->ell_val, im.col, im.val, im.g,
+            k_linearize_convection<<<blocks, 256, 0, st>>>({f->cv, fr, pt}, f->n, im.w, mean, f->ell_val, im.col, im.val, im.g,
                                                            im.slot, f->shift, f->d, f->dp, f->mp);
             break;
     }
@@ -420,7 +486,122 @@ int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt,
     return 0;
 }
 
+__global__ void k_linearize_cursor(int* __restrict__ words, int next, int count) {
+    words[0] = next;
+    words[1] = count;
+}
+
+}  // namespace
+
+void pnmol_reaction_free_ws(pnmol_filter* f) {
+    free_term_image(f);
+    free_linearize_table(f);
+}
+
+int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt, bool loop_step) {
+    // only a step of the loop takes its point from the table: the words that name the row belong to the running call
+    const LinearizeDev* l = loop_step ? f->lin_plan : nullptr;
+    const PointSource pt = l ? PointSource{l->table, l->words, f->ctr, f->d} : PointSource{nullptr, nullptr, nullptr, f->d};
+    return enqueue_linearize(f, mean, frame_dt, dt, pt);
+}
+
+int pnmol_linearize_begin(pnmol_filter* f, int k) {
+    if (!f->lin_plan) return 0;
+    const std::string why = linearize_plan_begin(f->lin_plan->plan, k);
+    if (why.empty()) return 0;
+    f->ctx->err = "pnmol_filter_steps_begin: linearisation points: " + why;
+    return -1;
+}
+
+int pnmol_linearize_enqueue_cursor(pnmol_filter* f) {
+    LinearizeDev* l = f->lin_plan;
+    if (!l) return 0;
+    k_linearize_cursor<<<1, 1, 0, f->ctx->stream>>>(l->words, l->plan.next, l->plan.count);
+    HIPCHK(f->ctx, hipGetLastError());
+    return 0;
+}
+
+void pnmol_linearize_collect(pnmol_filter* f, int k, bool ok) {
+    if (f->lin_plan) linearize_plan_collect(&f->lin_plan->plan, k, ok);
+}
+
+int pnmol_linearize_cursor(const pnmol_filter* f) { return f->lin_plan ? f->lin_plan->plan.next : 0; }
+
+void pnmol_linearize_rewind(pnmol_filter* f, int next) {
+    if (f->lin_plan) linearize_plan_rewind(&f->lin_plan->plan, next);
+}
+
 extern "C" {
+
+int pnmol_filter_set_linearization_points(pnmol_filter* f, int count, const double* u_cd) {
+    static const char* who = "pnmol_filter_set_linearization_points: ";
+    if (!f) return -1;
+    pnmol_ctx* ctx = f->ctx;
+    const std::string why = linearize_plan_validate(count, u_cd, f->d, has_term(f), f->pending_state != nullptr);
+    if (!why.empty()) return refuse(f, who, why);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a launch that reads the table may still be in flight)
+    if (count == 0 || !u_cd) {
+        if (f->lin_plan) {
+            pnmol_drop_graphs(f);  // (the loop's linearise launches take another argument with a table)
+            free_linearize_table(f);
+        }
+        return 0;
+    }
+    LinearizeDev* l = f->lin_plan;
+    if (!l || count > l->cap) {  // (a table that fits is overwritten in place: the captured graphs address it through the words)
+        LinearizeDev* fresh = new LinearizeDev();
+        hipError_t e = hipMalloc(&fresh->table, sizeof(double) * (size_t)count * (size_t)f->d);
+        if (e == hipSuccess) e = hipMalloc(&fresh->words, 2 * sizeof(int));
+        if (e == hipSuccess) e = hipMemset(fresh->words, 0, 2 * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(fresh->table, u_cd, sizeof(double) * (size_t)count * (size_t)f->d, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {  // (nothing is installed: the table set before, if any, stays as it was)
+            ctx->err = std::string(who) + hipGetErrorString(e);
+            for (void* q : {(void*)fresh->table, (void*)fresh->words})
+                if (q) (void)hipFree(q);
+            delete fresh;
+            return e == hipErrorOutOfMemory ? -4 : -2;
+        }
+        fresh->cap = count;
+        pnmol_drop_graphs(f);
+        free_linearize_table(f);
+        f->lin_plan = l = fresh;
+    } else {
+        const hipError_t e = hipMemcpy(l->table, u_cd, sizeof(double) * (size_t)count * (size_t)f->d, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {  // (the table is half overwritten: no table is left set)
+            ctx->err = std::string(who) + hipGetErrorString(e);
+            pnmol_drop_graphs(f);
+            free_linearize_table(f);
+            return -2;
+        }
+    }
+    linearize_plan_fill(&l->plan, count, u_cd);
+    return 0;
+}
+
+int pnmol_filter_linearization_pending(const pnmol_filter* f, int* next, int* count) {
+    if (!f) return -1;
+    if (next) *next = f->lin_plan ? f->lin_plan->plan.next : 0;
+    if (count) *count = f->lin_plan ? f->lin_plan->plan.count : 0;
+    return 0;
+}
+
+int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d) {
+    static const char* who = "pnmol_filter_linearize_at: ";
+    if (!f) return -1;
+    pnmol_ctx* ctx = f->ctx;
+    if (!u_d) return refuse(f, who, "bad argument (null point)");
+    if (!has_term(f)) return refuse(f, who, "no term set (pnmol_filter_set_reaction, _set_reaction_system, _set_convection)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the staging buffer of pnmol_filter_set_operator_diagonal (refused while a term is set, so free for this): the kernels read the
+    // mapped host memory as a table of one row.  It may still be read by the previous call's launch: wait for that launch.
+    HIPCHK(ctx, hipEventSynchronize(f->ev_op));
+    std::memcpy(f->h_op, u_d, sizeof(double) * (size_t)f->d);
+    if (int rc = enqueue_linearize(f, nullptr, 0.0, 1.0, PointSource{f->h_op_dev, nullptr, nullptr, f->d})) return rc;
+    HIPCHK(ctx, hipEventRecord(f->ev_op, ctx->stream));
+    f->sq_dt = -1.0;  // the operator changed: pnmol_filter_prepare_error_model comes next
+    return 0;
+}
 
 int pnmol_filter_set_reaction(pnmol_filter* f, const pnmol_reaction* r) {
     static const char* who = "pnmol_filter_set_reaction: ";
@@ -492,7 +673,7 @@ int pnmol_filter_linearize(pnmol_filter* f, const pnmol_state* in, double dt) {
     pnmol_ctx* ctx = f->ctx;
     if (!has_term(f)) return refuse(f, who, "no reaction set (pnmol_filter_set_reaction)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (int rc = pnmol_reaction_enqueue(f, in->mean, in->frame_dt, dt)) return rc;
+    if (int rc = pnmol_reaction_enqueue(f, in->mean, in->frame_dt, dt, false)) return rc;
     f->sq_dt = -1.0;  // the operator changed: pnmol_filter_prepare_error_model comes next
     return 0;
 }

@@ -78,6 +78,9 @@ SYMBOLS = {
     "pnmol_filter_set_reaction_system": (ctypes.c_int, [_vp, _vp]),    # (pnmol_reaction_system*: SystemReactionDesc)
     "pnmol_filter_set_convection": (ctypes.c_int, [_vp, _vp, _c_double_p]),   # (pnmol_convection*: ConvectionDesc; G (d, d))
     "pnmol_filter_linearize": (ctypes.c_int, [_vp, _vp, ctypes.c_double]),
+    "pnmol_filter_set_linearization_points": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p]),
+    "pnmol_filter_linearization_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_filter_linearize_at": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
     "pnmol_state_clone": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
@@ -425,6 +428,36 @@ class Filter:
         """Enqueue the EK1 linearisation of the reaction at the predicted mean of a step from `state_in` over dt
         (`pnmol_filter_linearize`; no synchronisation).  Then `prepare_error_model(dt)`, then `step(state_in, dt)`."""
         self.ctx.check(self.lib.pnmol_filter_linearize(self.handle, state_in.handle, float(dt)), "pnmol_filter_linearize")
+        self.error_model_dt = None
+
+    def set_linearization_points(self, points):
+        """Linearisation points for the constant-step loop (`pnmol_filter_set_linearization_points`): `points` (count, d),
+        derivative 0 in raw coordinates; the i-th step `steps` takes from now on linearises the term at row i in place of its own
+        predicted mean.  The cursor starts at row 0."""
+        u = _f64(points)
+        if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] != self.d:
+            raise ValueError(f"points must be (count, {self.d}) with count >= 1, got {u.shape} "
+                             "(clear_linearization_points() drops the table)")
+        self.ctx.check(self.lib.pnmol_filter_set_linearization_points(self.handle, u.shape[0], _dp(u)),
+                       "pnmol_filter_set_linearization_points")
+
+    def clear_linearization_points(self):
+        """Drop the table: the filter then takes the launches and gives the bits of one that never had a table."""
+        self.ctx.check(self.lib.pnmol_filter_set_linearization_points(self.handle, 0, None),
+                       "pnmol_filter_set_linearization_points")
+
+    def linearization_pending(self):
+        """(next, count): the table's cursor -- the row the next step is linearised at -- and its number of rows ((0, 0): none)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.pnmol_filter_linearization_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
+                       "pnmol_filter_linearization_pending")
+        return nxt.value, n.value
+
+    def linearize_at(self, u):
+        """Enqueue the EK1 linearisation of the term at the point `u` (d,) (`pnmol_filter_linearize_at`; no synchronisation).  Then
+        `prepare_error_model(dt)` if the error estimate is wanted, then `step(state_in, dt)`."""
+        u = _f64(u, (self.d,))
+        self.ctx.check(self.lib.pnmol_filter_linearize_at(self.handle, _dp(u)), "pnmol_filter_linearize_at")
         self.error_model_dt = None
 
     def step(self, state_in, dt, want_error=True):

@@ -13,6 +13,7 @@ Documented deviations from the reference's numbers:
     z^T S^-1 z / m.
 """
 
+import collections
 import os
 
 import numpy as np
@@ -22,6 +23,13 @@ import scipy.sparse
 from . import _hip, pdefilter
 from .base import iwp, rv
 from .odetools import step as _step
+
+
+IteratedSolution = collections.namedtuple(
+    "IteratedSolution", "filtered means stds smoothed increments num_iterations converged data_log_likelihood data_log_likelihoods")
+IteratedSolution.__doc__ = """Result of `solve_iterated`: the last pass's filtering `PDESolution`, the smoothed means / stds (T+1, d),
+the `smooth()` solution of the last pass (or None), the relative increment of every pass beyond pass 0, their number, whether the
+last increment met the tolerance, and with observations the data log-likelihoods of the last pass (else None)."""
 
 
 class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
@@ -296,7 +304,32 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         ref = None if state.reference_state is None else np.abs(m_new[0][:observation.C.shape[1]])
         return state._replace(y=rv.DeviceMultivariateNormal(m_new, dev_out), reference_state=ref), res.log_likelihood
 
-    def solve_marginals(self, pde, *, num_steps=None, observations=None):
+    def _checked_linearization_points(self, pde, linearize_at, num_steps_taken):
+        """`linearize_at` as the (T, d) array the device takes, or None; refusals in front of any device work."""
+        if linearize_at is None:
+            return None
+        if self._reaction_for_device(pde) is None:
+            raise TypeError("linearize_at needs a term the device linearises (SemiLinearWhiteNoiseEK1, fp64 covariance form, "
+                            "a problem with `pde.reaction`, reaction_on_device=True)")
+        pts = np.ascontiguousarray(np.asarray(linearize_at, dtype=np.float64))
+        want = (num_steps_taken, pde.L.shape[0])
+        if pts.shape != want:
+            raise ValueError(f"linearize_at must have shape {want} -- one row per step of the constant schedule, a runt last "
+                             f"step included --, got {pts.shape}")
+        if not np.all(np.isfinite(pts)):
+            raise ValueError("linearize_at has entries that are not finite")
+        return pts
+
+    def _clear_quietly(self, *clears):
+        """The loop's options off again behind a solve; a failure of the solve is the one to report, not one of a clear."""
+        for clear in clears:
+            try:
+                if clear is not None:
+                    clear()
+            except _hip.PnmolHipError:
+                pass
+
+    def solve_marginals(self, pde, *, num_steps=None, observations=None, linearize_at=None):
         """Constant-step solve that keeps everything on the device: returns
         (t (T+1,), means (T+1,d), stds (T+1,d), diffusion_squared_local (T,), final PDEFilterState).
 
@@ -309,13 +342,26 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         (`pnmol_filter_set_observations`), and the rows of `means` / `stds` are those of the conditioned
         states.  The result then has a sixth element `info = dict(num_steps, data_log_likelihood, data_log_likelihoods)`, as
         `solve(pde, observations=...)` reports them.  Per-time sensor arrays stay with `solve()`.
+
+        linearize_at (beyond the reference; problems whose term the device linearises): (T, d), row k the point at which the step
+        that lands on `t[k+1]` linearises the term, in place of its own predicted mean (`pnmol_filter_set_linearization_points`,
+        DESIGN.md section 22).  None: the EK1 of the reference.
         """
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_marginals needs the Constant step rule")
         if observations is not None:
-            return self._solve_marginals_observed(pde, num_steps, observations)
+            return self._solve_marginals_observed(pde, num_steps, observations, linearize_at)
         ts, dts = self._constant_schedule(pde, num_steps)
-        return self._run_device_loop(pde, self.initialize(pde), ts, dts)
+        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
+        state = self.initialize(pde)
+        if pts is None or not dts:
+            return self._run_device_loop(pde, state, ts, dts)
+        flt = self._device_filter
+        try:
+            flt.set_linearization_points(pts)
+            return self._run_device_loop(pde, state, ts, dts)
+        finally:
+            self._clear_quietly(flt.clear_linearization_points)
 
     def _constant_schedule(self, pde, num_steps):
         """(times, steps) of the constant-step loop: the t-accumulation of the reference, a runt final step included."""
@@ -353,7 +399,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                                          diffusion_squared_local=sig[-1] if sig else [])
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
 
-    def _solve_marginals_observed(self, pde, num_steps, observations):
+    def _solve_marginals_observed(self, pde, num_steps, observations, linearize_at=None):
         """`solve_marginals` with sensor data: everything is validated on the host before `initialize` binds the device."""
         from . import data
 
@@ -361,6 +407,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
         dt0 = self.steprule.first_dt(pde)
         ts, dts = self._constant_schedule(pde, num_steps)
+        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
         if obs:
             times, C, R, ys = data.shared_sensors(obs)
             if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
@@ -376,6 +423,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             if obs and times.size:
                 Cd = C if C.shape[1] == flt.ds else np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
                 flt.set_observations(times, Cd, ys, R)
+            if pts is not None and dts:
+                flt.set_linearization_points(pts)
             out = self._run_device_loop(pde, state, ts, dts)
             applied, nobs = flt.observations_pending()
             if applied != nobs:
@@ -386,13 +435,16 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 flt.clear_observations()
             except _hip.PnmolHipError:
                 pass
+            self._clear_quietly(flt.clear_linearization_points if pts is not None else None)
             raise
         flt.clear_observations()
+        if pts is not None:
+            flt.clear_linearization_points()
         info = dict(num_steps=len(dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
         return out + (info,)
 
     # ------------------------------------------------------------------ the device loop with the trajectory kept
-    def solve_on_device(self, pde, *, num_steps=None, observations=None):
+    def solve_on_device(self, pde, *, num_steps=None, observations=None, linearize_at=None):
         """`solve()` of the `Constant` rule through the device-resident loop: a `PDESolution` with the time grid of
         `solve_marginals` (a runt last step included), `mean` (T+1, n, d_state), device-resident states, the calibrated
         diffusion as `solve()` computes it and `info = dict(num_steps)` -- with `observations` (as in `solve_marginals`) also
@@ -402,7 +454,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         The loop records the state behind every step into one device state per grid time (`pnmol_filter_set_recorder`, DESIGN.md
         section 20): no host round trip per step, one read-back of all means per run of equal steps.  It accepts what
         `solve_marginals` accepts (linear problems, problems whose term the device linearises, one sensor array) in the fp64
-        covariance form; memory: T + 1 states of (n d)^2 doubles on the device."""
+        covariance form; memory: T + 1 states of (n d)^2 doubles on the device.  linearize_at: as in `solve_marginals`."""
         from . import data, sqrtform
 
         if not isinstance(self.steprule, _step.Constant):
@@ -415,6 +467,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             self._check_observations_supported()
             obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
         ts, dts = self._constant_schedule(pde, num_steps)
+        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
         if obs:
             times, C, R, ys = data.shared_sensors(obs)
             if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
@@ -437,12 +490,16 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             sig = np.zeros(0)
             if slots:
                 flt.set_recorder(slots)
+                if pts is not None:
+                    flt.set_linearization_points(pts)
                 # (the loop advances its state in place: it works on a copy, the initial state stays what `ys[0]` holds)
                 work = state._replace(y=rv.DeviceMultivariateNormal(first.mean, first.device_state.clone()))
                 _, _, _, sig, _ = self._run_device_loop(pde, work, ts, dts)
                 filled, count = flt.recorder_pending()
                 if filled != count:
                     raise RuntimeError(f"{count - filled} step(s) of the loop were not recorded")
+                if pts is not None and flt.linearization_pending() != (len(dts), len(dts)):
+                    raise RuntimeError("the loop did not consume every linearisation point")
                 means = flt.recorder_means(0, count)            # one read-back for all states
             else:
                 means = np.zeros((0,) + first.mean.shape)
@@ -452,7 +509,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                     raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
                 lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
         finally:
-            for clear in (flt.clear_recorder, flt.clear_observations if planned else None):
+            for clear in (flt.clear_recorder, flt.clear_observations if planned else None,
+                          flt.clear_linearization_points if pts is not None else None):
                 try:                                            # (a failure above is the one to report, not one of the clear)
                     if clear is not None:
                         clear()
@@ -476,6 +534,61 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             y = ys[0]
             return y.mean[:1, :flt.d].copy(), np.sqrt(np.maximum(y.marginal_var[:1, :flt.d], 0.0))
         return flt.smoother_steps([y.device_state for y in ys], np.diff(t))
+
+    # ------------------------------------------------------------------ iterated smoother
+    def solve_iterated(self, pde, *, iterations=10, tol=1e-9, num_steps=None, observations=None, relaxation=1.0, start=None,
+                       smooth="marginal"):
+        """Iterated extended Kalman smoother (IEKS; beyond the reference): forward and backward passes repeated, every step of a
+        forward pass linearised at the previous pass's SMOOTHED mean, until the trajectory stops moving.  The fixed point is the
+        MAP trajectory under prior, PDE residuals and sensor data (Gauss-Newton on that objective).
+
+        Pass 0 is `solve_on_device(pde)` -- the EK1, linearised at the predicted means -- or, with `start` (T, d),
+        `solve_on_device(pde, linearize_at=start)`.  Behind every pass `smooth_marginals` gives the smoothed means `ms` (T+1, d),
+        and the next pass linearises at u <- u + relaxation (ms[1:] - u), u being `start` or, without one, `ms[1:]` of pass 0.  The
+        increment of a pass is max|ms_new - ms_old| / max|ms_new|; the loop ends when it is <= tol, or after `iterations` passes
+        beyond pass 0.  Every pass starts from `initialize(pde)`'s state, whose update on the PDE residual at t0 keeps its own
+        linearisation (at the prior mean conditioned on y0): the initial state is not iterated.
+
+        Returns an `IteratedSolution`: `filtered` (the last pass's `PDESolution`: `smooth`, `sample`, `sample_dense` and
+        `solution(t)` work on it), `means` / `stds` (T+1, d) smoothed, `smoothed` (`smooth(filtered, dense=smooth)`, or None
+        for smooth=None), `increments`, `num_iterations`, `converged`, and with observations `data_log_likelihood(s)` of the last
+        pass.  One forward solution is alive at a time: memory is that of `solve_on_device`.  Supported: `SemiLinearWhiteNoiseEK1`
+        in the fp64 covariance form with a term the device linearises, `Constant` steps."""
+        from . import latent, sqrtform
+
+        if not isinstance(self.steprule, _step.Constant):
+            raise TypeError("solve_iterated needs the Constant step rule")
+        if (not isinstance(self, SemiLinearWhiteNoiseEK1) or isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin))
+                or self.dtype != "f64" or self._reaction_for_device(pde) is None):
+            raise TypeError(f"solve_iterated() supports pnmol.white.SemiLinearWhiteNoiseEK1 in the fp64 covariance form on a problem "
+                            f"whose term the device linearises (`pde.reaction`, reaction_on_device=True); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} on this problem is not that")
+        if smooth not in (None, "marginal", "full"):
+            raise ValueError(f'solve_iterated(): smooth must be None, "marginal" or "full", got {smooth!r}')
+        if int(iterations) < 0 or not tol >= 0.0 or not 0.0 < relaxation <= 1.0:
+            raise ValueError("solve_iterated(): needs iterations >= 0, tol >= 0 and 0 < relaxation <= 1")
+        _, dts = self._constant_schedule(pde, num_steps)
+        points = self._checked_linearization_points(pde, start, len(dts))
+        kw = dict(num_steps=num_steps, observations=observations)
+        sol = self.solve_on_device(pde, linearize_at=points, **kw)
+        ms, sd = self.smooth_marginals(sol)
+        if points is None:
+            points = ms[1:].copy()
+        increments = []
+        converged = not dts                                     # (no step: nothing to iterate)
+        while not converged and len(increments) < int(iterations):
+            points = points + relaxation * (ms[1:] - points)
+            del sol                                             # (the states of the pass before: one forward solution at a time)
+            sol = self.solve_on_device(pde, linearize_at=points, **kw)
+            ms_new, sd = self.smooth_marginals(sol)
+            increments.append(float(np.abs(ms_new - ms).max() / np.abs(ms_new).max()))
+            ms = ms_new
+            converged = increments[-1] <= tol
+        smoothed = None if smooth is None else self.smooth(sol, dense=smooth)
+        return IteratedSolution(filtered=sol, means=ms, stds=sd, smoothed=smoothed, increments=increments,
+                                num_iterations=len(increments), converged=converged,
+                                data_log_likelihood=sol.info.get("data_log_likelihood"),
+                                data_log_likelihoods=sol.info.get("data_log_likelihoods"))
 
     # ------------------------------------------------------------------ backward walks (smoothing, joint draws)
     def _walk_inputs(self, who, solution):
@@ -669,12 +782,12 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return None
         return reaction
 
-    def solve_marginals(self, pde, *, num_steps=None, observations=None):
+    def solve_marginals(self, pde, *, num_steps=None, observations=None, linearize_at=None):
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
-        return super().solve_marginals(pde, num_steps=num_steps, observations=observations)
+        return super().solve_marginals(pde, num_steps=num_steps, observations=observations, linearize_at=linearize_at)
 
-    def solve_on_device(self, pde, *, num_steps=None, observations=None):
+    def solve_on_device(self, pde, *, num_steps=None, observations=None, linearize_at=None):
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_on_device keeps the loop on the device and needs a linear PDE; use solve()")
-        return super().solve_on_device(pde, num_steps=num_steps, observations=observations)
+        return super().solve_on_device(pde, num_steps=num_steps, observations=observations, linearize_at=linearize_at)
