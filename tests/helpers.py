@@ -6,11 +6,13 @@ import pnmol
 import pnmol_oracle as oracle
 
 
-def make_pair(N, nu, dt, K, bcond="dirichlet", dx=None, kappa=0.05, canonical=True):
-    """Same heat problem + solver in the product (`pnmol`) and in the oracle."""
+def make_pair(N, nu, dt, K, bcond="dirichlet", dx=None, kappa=0.05, canonical=True, bbox=None):
+    """Same heat problem + solver in the product (`pnmol`) and in the oracle.  bbox: the domain (default [0, 1])."""
     dx = 1.0 / (N - 1) if dx is None else dx
     kw = dict(tmax=K * dt, dx=dx, diffusion_rate=kappa, bcond=bcond, stencil_size_interior=3,
               stencil_size_boundary=3, nugget_gram_matrix_fd=0.0)
+    if bbox is not None:
+        kw["bbox"] = list(bbox)
     pde = pnmol.pde.examples.heat_1d_discretized(kernel=pnmol.kernels.SquareExponential(), **kw)
     solver = pnmol.white.LinearWhiteNoiseEK1(
         num_derivatives=nu, steprule=pnmol.odetools.step.Constant(dt),
