@@ -30,7 +30,8 @@
  *     `pnmol_smoother_step_bridge`, `pnmol_bridge_*`, `pnmol_samples_interpolate`, `pnmol_samples_clone`) and the measurement
  *     update (`pnmol_state_observe`), the recorder of the constant-step loop (`pnmol_filter_set_recorder`, `_recorder_pending`,
  *     `_recorder_means`), the one-call backward pass (`pnmol_smoother_steps`) and the linearisation points of the loop
- *     (`pnmol_filter_set_linearization_points`, `_linearization_pending`, `pnmol_filter_linearize_at`).
+ *     (`pnmol_filter_set_linearization_points`, `_linearization_pending`, `pnmol_filter_linearize_at`) and the posterior of
+ *     linear functionals of the trajectory (`pnmol_functionals`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -531,6 +532,24 @@ int pnmol_filter_recorder_means(pnmol_filter* f, int first, int count, double* m
  * `pnmol_smoother_step_bridge`. */
 int pnmol_smoother_steps(pnmol_filter* f, int T, pnmol_state* const* filt, const double* dt_T, pnmol_state* const* out,
                          double* means_T1d, double* stds_T1d, int* info_T);
+
+/* The exact smoothing posterior of Q linear functionals of the whole trajectory, q = sum_k W_k x_k (k = 0 .. T, x_k the state at
+ * filt[k]->t, W_k: Q x D): mean_Q (Q) and cov_QQ (Q x Q row-major, symmetric to the bit), uncalibrated like every covariance here.
+ * filt (T+1 states) and dt_T as for `pnmol_smoother_steps`; w_QT1nd: the weights, (Q, T+1, n, d) row-major in raw coordinates --
+ * entry (q, k, a, j) multiplies derivative a at mesh point j of x_k.  Only the filtered states enter: the adjoint of the backward
+ * recursion behind `pnmol_smoother_step` runs in ascending k (csrc/pnmol_functional.hip has the recursion), so no smoothed state
+ * and no gain is formed.  Per step one sweep of [P-; (A U)^T] (the Cholesky factorisation of the predicted covariance with
+ * PNMOL_FUNCTIONALS_MAX_Q extra rows) and work that is thin in Q; the T steps are enqueued back to back on the ctx stream with ONE
+ * synchronisation at the end.  T = 0 is valid: W_0 m_0 and W_0 P_0 W_0^T.  The workspace ((3 Dp + 320) Dp doubles and the
+ * weights of the largest call) is allocated on the first call and freed with the filter.  The states are only read; a recorder, an
+ * observation plan, a term, linearisation points and the captured graphs of the filter are not touched.
+ * Returns 0; -2 / -3 of the first failing step (`pnmol_last_error` names it), the outputs are untouched then; -4 out of memory;
+ * -1 before anything is enqueued, with the reason in `pnmol_last_error`: a null pointer, Q < 1, Q > PNMOL_FUNCTIONALS_MAX_Q,
+ * T < 0, dt <= 0 or not finite, weights that are not finite, a null or foreign state, a latent-force or fp32 filter, a call
+ * between `pnmol_filter_steps_begin` and `_end`. */
+#define PNMOL_FUNCTIONALS_MAX_Q 64
+int pnmol_functionals(pnmol_filter* f, int T, pnmol_state* const* filt, const double* dt_T, int Q, const double* w_QT1nd,
+                      double* mean_Q, double* cov_QQ);
 
 /* Optional: do the one-off host work of a following `pnmol_filter_steps(f, s, k, dt, ...)` now
  * (output buffers, capture + instantiation of the hipGraphs the step loop is replayed from). */

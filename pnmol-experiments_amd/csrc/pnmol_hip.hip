@@ -3873,6 +3873,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_sample_free_ws(f);
     pnmol_dense_free_ws(f);
     pnmol_observe_free_ws(f);
+    pnmol_functional_free_ws(f);
     pnmol_observe_plan_free(f);
     pnmol_record_free(f);
     pnmol_reaction_free_ws(f);

@@ -212,6 +212,8 @@ struct pnmol_filter {
     // Linearisation points of the constant-step loop (pnmol_filter_set_linearization_points, pnmol_reaction.hip): NULL = none, every
     // step is linearised at its own predicted mean.  While a table is set the i-th step taken since is linearised at its row i.
     struct LinearizeDev* lin_plan = nullptr;
+    // Linear functionals of the trajectory (pnmol_functionals, pnmol_functional.hip): the workspace of the pass, allocated on first use
+    struct FunctionalWs* fn_ws = nullptr;
 };
 inline bool has_term(const pnmol_filter* f) { return f->term != TermKind::none; }
 
@@ -282,6 +284,7 @@ void pnmol_smooth_free_ws(pnmol_filter* f);
 void pnmol_sample_free_ws(pnmol_filter* f);
 void pnmol_dense_free_ws(pnmol_filter* f);
 void pnmol_observe_free_ws(pnmol_filter* f);
+void pnmol_functional_free_ws(pnmol_filter* f);
 // pnmol_smooth.hip: the smoother's workspace, allocated on first use (a backward sampling step runs its main sweep there)
 int pnmol_smooth_ensure_ws(pnmol_filter* f);
 

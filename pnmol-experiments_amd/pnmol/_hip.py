@@ -128,6 +128,8 @@ SYMBOLS = {
     "pnmol_filter_recorder_means": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_double_p]),
     "pnmol_smoother_steps": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp), _c_double_p, ctypes.POINTER(_vp),
                                             _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_functionals": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp), _c_double_p, ctypes.c_int, _c_double_p,
+                                         _c_double_p, _c_double_p]),
     "pnmol_filter_prepare_steps": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double]),
     "pnmol_filter_last_steps_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "pnmol_filter_prepare_error_model": (ctypes.c_int, [_vp, ctypes.c_double]),
@@ -598,6 +600,25 @@ class Filter:
         rc = self.lib.pnmol_smoother_steps(self.handle, T, filt, _dp(dts), outs, _dp(means), _dp(stds), info)
         self.ctx.check(rc, "pnmol_smoother_steps")
         return (means, stds, out) if keep else (means, stds)
+
+    def functionals(self, states, dts, weights):
+        """(mean (Q,), cov (Q, Q)) of the Q linear functionals sum_k weights[:, k] . x_k of the trajectory under the smoothing
+        posterior (`pnmol_functionals`): `states` the T+1 filtered States, `dts` the T steps between them, `weights`
+        (Q, T+1, n, d) in raw coordinates.  One call, one synchronisation; the states are only read."""
+        states = list(states)
+        T = len(states) - 1
+        dts = _f64(np.atleast_1d(dts)) if T > 0 else np.zeros(0)
+        weights = _f64(weights)
+        if T < 0 or dts.shape != (T,):
+            raise ValueError(f"functionals needs T + 1 >= 1 states and T step sizes, got {len(states)} and {dts.shape}")
+        if weights.ndim != 4 or weights.shape[1:] != (T + 1, self.n, self.d) or weights.shape[0] < 1:
+            raise ValueError(f"functionals: weights must be (Q, {T + 1}, {self.n}, {self.d}), got {weights.shape}")
+        Q = weights.shape[0]
+        filt = (_vp * (T + 1))(*[None if s is None else s.handle for s in states])
+        mean, cov = np.empty(Q), np.empty((Q, Q))
+        rc = self.lib.pnmol_functionals(self.handle, T, filt, _dp(dts) if T > 0 else None, Q, _dp(weights), _dp(mean), _dp(cov))
+        self.ctx.check(rc, "pnmol_functionals")
+        return mean, cov
 
     def predict(self, state, dt):
         """The prior alone carried over dt > 0 from `state` (`pnmol_state_predict`): a new State at state.t + dt."""

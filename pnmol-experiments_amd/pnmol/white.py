@@ -642,6 +642,26 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                                      diffusion_squared_calibrated=solution.diffusion_squared_calibrated, bridges=bridges,
                                      smoothed=True)
 
+    # ------------------------------------------------------------------ functionals of the trajectory
+    def functionals(self, solution, weights, *, calibrated=False):
+        """The exact smoothing posterior of linear functionals q = sum_k weights[:, k] . x_k of the whole trajectory of a
+        `solve()` or `solve_on_device()` result: time integrals, space-time means, differences across times (builders:
+        `pnmol.functionals`).  weights: (Q, T+1, d) on the PDE solution at the T+1 grid times, or (Q, T+1, n, d) on all
+        derivatives, raw coordinates; Q <= 64.  Returns a `pnmol.functionals.FunctionalPosterior` (`mean` (Q,), `cov` (Q, Q),
+        `std`), uncalibrated like `smooth`; calibrated=True scales `cov` by `solution.diffusion_squared_calibrated`.
+
+        One `pnmol_functionals` call on the filter that owns `solution`'s device-resident states: only the filtered states enter
+        (the adjoint of the recursion behind `smooth`, in ascending time), nothing is smoothed, drawn or
+        read back but the result.  `solution` is unchanged.  Supported: what `smooth` supports."""
+        from . import functionals as _fn
+
+        ys, flt = self._walk_inputs("functionals", solution)
+        w = _fn.checked_weights(weights, len(ys) - 1, flt.n, flt.d)
+        mean, cov = flt.functionals([y.device_state for y in ys], np.diff(np.asarray(solution.t, dtype=np.float64)), w)
+        if calibrated:
+            cov = cov * solution.diffusion_squared_calibrated
+        return _fn.FunctionalPosterior(mean=mean, cov=cov)
+
     # ------------------------------------------------------------------ joint draws
     def sample(self, solution, num_samples, *, seed=0, noise=None, calibrated=False):
         """Joint draws of whole trajectories from the smoothing posterior of a `solve()` result.
