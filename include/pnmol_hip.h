@@ -31,7 +31,8 @@
  *     update (`pnmol_state_observe`), the recorder of the constant-step loop (`pnmol_filter_set_recorder`, `_recorder_pending`,
  *     `_recorder_means`), the one-call backward pass (`pnmol_smoother_steps`) and the linearisation points of the loop
  *     (`pnmol_filter_set_linearization_points`, `_linearization_pending`, `pnmol_filter_linearize_at`) and the posterior of
- *     linear functionals of the trajectory (`pnmol_functionals`).
+ *     linear functionals of the trajectory (`pnmol_functionals`), and the forcing of driven problems
+ *     (`pnmol_filter_set_forcing`, `_forcing_pending`, `pnmol_filter_force_at`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -244,6 +245,43 @@ int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, c
 int pnmol_filter_set_linearization_points(pnmol_filter* f, int count, const double* u_cd);
 int pnmol_filter_linearization_pending(const pnmol_filter* f, int* next, int* count);
 int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d);
+
+/* Driven problems: sources and boundary values --------------------------------------------------------------------------------
+ * u_t = L u + r(u) + s(t, x) with boundary rows B u = g(t).  With rhs(t) = [s(t, X) (d); g(t) (nB)], m = d + nB numbers, the step
+ * that lands on t measures z = H m^- + shift_term - rhs(t): `shift_term` is what the filter has without forcing (zero for a linear
+ * filter, J u - r behind `pnmol_filter_linearize`), and the device forms fl(shift_term[i] - rhs[i]), one rounded subtraction per row
+ * (without a term: -rhs[i], exact).  The PDE rows are the reference's semilinear model with f <- f + s (white.py:189-208); the
+ * reference knows B u = 0 only.  H, S, the gain, the error model and the whole backward pass are untouched: forcing enters the
+ * means only.  For fp64 filters, white-noise and latent-force (d_state = 2 d) -- the filters that take
+ * `pnmol_filter_set_observations`.
+ * `pnmol_filter_set_forcing(f, count, rhs_cm)`: rhs_cm is (count, m) row-major; row k is consumed by the k-th step
+ * `pnmol_filter_steps(_begin)` takes from now on.  Rows are consumed across calls (a schedule's runt last step takes its own row);
+ * a call that fails (-2 / -3) consumes none, `pnmol_filter_prepare_steps` consumes none.  The table is copied to the device (row
+ * stride mp, padding zero), the cursor goes to row 0; the call synchronises and drops the captured graphs.  The row is addressed on
+ * the device (a cursor word written once per call plus the loop's step counter), so every step launches with identical arguments and
+ * the loop's graphs serve any position.  While a table is set the loop takes the self-contained steps (as with a term or a sensor
+ * plan: the next innovation cannot be prepared before its right-hand side is in place).  Without a term H does not change, and the
+ * loop KEEPS the error model: `error_sigma2` is reported as in the unforced loop when `pnmol_filter_prepare_error_model(dt)` was
+ * called; with a term the loop carries none, as ever.  Composes with a term, the table of linearisation points, the recorder and
+ * the sensor plan; the order per step is linearise, force, step, observation update, record.  The term setters keep the table: it
+ * belongs to the problem, not to the term.  count = 0 or a NULL table clears.  A filter without forcing enqueues what it always
+ * did.  -1 (reason in `pnmol_last_error`, nothing enqueued): null filter, fp32 filter, count < 0, an entry that is not finite (row
+ * and column are named), called between `pnmol_filter_steps_begin` and `_end`; and from `pnmol_filter_steps(_begin)`: more steps
+ * asked for than rows left (the state is untouched).  -4: out of memory.
+ * `pnmol_filter_forcing_pending`: the cursor (the row the next step takes) and the number of rows (0, 0: no table).
+ * `pnmol_filter_force_at(f, rhs_m)`: the single-step counterpart -- every `pnmol_filter_step` from now on measures against these m
+ * numbers, until another call replaces them or NULL returns the filter to unforced.  `pnmol_filter_step` reads the shift as it
+ * stands when it is enqueued, so with a term call `pnmol_filter_linearize` / `_linearize_at` first, in any order with this call.
+ * `error_sigma2` and the error estimate are reported as without forcing.  No synchronisation (the numbers wait in mapped host
+ * memory of their own).  The loop takes no notice of it, and `pnmol_filter_step` takes none of the table.  A right-hand side
+ * PERSISTS: it is not consumed by a step, it survives `pnmol_filter_steps`, `pnmol_filter_set_forcing` and the term setters, and
+ * while it is held the operator setters refuse (below) -- `pnmol_filter_force_at(f, NULL)` behind the last forced step is the
+ * caller's job.  -1: null filter, fp32 filter, an entry that is not finite, called between `pnmol_filter_steps_begin` and `_end`.
+ * While a table or a single right-hand side is set, `pnmol_filter_set_operator` and `pnmol_filter_set_operator_diagonal` return
+ * -1, as they do with a term. */
+int pnmol_filter_set_forcing(pnmol_filter* f, int count, const double* rhs_cm);
+int pnmol_filter_forcing_pending(const pnmol_filter* f, int* next, int* count);
+int pnmol_filter_force_at(pnmol_filter* f, const double* rhs_m);
 
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);

@@ -3107,9 +3107,10 @@ enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 // (pnmol_filter_set_observations): z and G of the step behind an update would come from the unconditioned state, and the fused
 // steps write P only in the call's last step, while the update conditions P itself.  Nor while a recorder is set
 // (pnmol_filter_set_recorder): it copies the posterior P behind every step, which the fused steady-state launch never writes.
+// Nor while a table of right-hand sides is set (pnmol_filter_set_forcing): the next step's z needs that step's row in place.
 inline bool fused_loop(const pnmol_filter* f) {
     return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f) && !pnmol_observe_plan_pending(f) &&
-           !pnmol_record_active(f);
+           !pnmol_record_active(f) && !pnmol_forcing_table_set(f);
 }
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
@@ -3170,8 +3171,9 @@ inline bool short_last_panel() {  // PNMOL_HIP_SHORT_LAST=0: A/B switch
 }
 template <int N>
 int launch_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout,
-                double* mout, double* varout, bool record, StepKind kind) {
+                double* mout, double* varout, bool record, StepKind kind, const double* forced_shift) {
     pnmol_ctx* ctx = f->ctx;
+    const double* shift = forced_shift ? forced_shift : f->shift;  // (a driven step: pnmol_forcing.hip)
     hipStream_t st = ctx->stream;
     IwpConsts c = f->iwp;
     for (int a = 0; a < f->n; ++a) {
@@ -3188,7 +3190,7 @@ int launch_step(pnmol_filter* f, const double* Pin, const double* min, double fr
     //  k_readout launch did the vector part)
     if (kind != STEP_STEADY)
         k_predict<N><<<dim3(dp / 32, dp / 8 + 1), dim3(32, 8), sizeof(double) * Dp, st>>>(
-        Pin, f->Ppred, f->Kg, c, dp, min, f->mpred, f->shift, f->G, f->zbuf, mm, f->ctr, f->flags, f->nflags, f->p32);
+        Pin, f->Ppred, f->Kg, c, dp, min, f->mpred, shift, f->G, f->zbuf, mm, f->ctr, f->flags, f->nflags, f->p32);
     // K2: G = [S; P-H^T; z; I]  (STEADY: done by the previous step's k_readout launch)
     if (kind != STEP_STEADY) {
         if (f->ellw > HW) {
@@ -3247,7 +3249,7 @@ int launch_step(pnmol_filter* f, const double* Pin, const double* min, double fr
     // K5: read-out + deterministic reduction of the per-row partial sums
     IwpConsts cn = f->iwp;  // the next step of the loop has the same dt: no frame change
     for (int a = 0; a < MAXN; ++a) cn.ts[a] = 1.0;
-    RoleArgs ra{cn, dp, mout, f->mpred, f->shift, f->G, f->zbuf, mm, f->flags, f->nflags};
+    RoleArgs ra{cn, dp, mout, f->mpred, shift, f->G, f->zbuf, mm, f->flags, f->nflags};
     const unsigned rblocks = (f->d + 255) / 256;
     if (kind == STEP_FULL)
         k_readout<N, false><<<rblocks, 256, 0, st>>>(mout, varout, record ? f->rec_means : nullptr,
@@ -3267,17 +3269,18 @@ int launch_step(pnmol_filter* f, const double* Pin, const double* min, double fr
 }
 
 int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout,
-                  double* mout, double* varout, bool record, StepKind kind = STEP_FULL) {
+                  double* mout, double* varout, bool record, StepKind kind = STEP_FULL, const double* forced_shift = nullptr) {
     switch (f->n) {
-        case 2: return launch_step<2>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind);
-        case 3: return launch_step<3>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind);
-        case 4: return launch_step<4>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind);
+        case 2: return launch_step<2>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind, forced_shift);
+        case 3: return launch_step<3>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind, forced_shift);
+        case 4: return launch_step<4>(f, Pin, min, frame_dt, dt, Pout, mout, varout, record, kind, forced_shift);
     }
     return -1;
 }
 
 // a step of the constant-step loop: with a reaction set the operator is re-linearised at this step's predicted mean first
 // (k_linearize, pnmol_reaction.hip; with a table of linearisation points set: at the table's row for this step); with a
+// table of right-hand sides set the step measures against its row (k_force, pnmol_forcing.hip); with a
 // recorder set the state behind the step goes into its slot (k_record, pnmol_record.hip; keep = false: a sensor update follows
 // at once and the caller records behind it)
 int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
@@ -3285,7 +3288,11 @@ int loop_step(pnmol_filter* f, const double* Pin, const double* min, double fram
     if (has_term(f)) {
         if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt, true)) return rc;
     }
-    if (int rc = dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind)) return rc;
+    // a table of right-hand sides: this step's row goes into the shift it measures with (k_force, pnmol_forcing.hip)
+    int frc = 0;
+    const double* forced_shift = pnmol_forcing_enqueue_loop(f, &frc);
+    if (frc != 0) return frc;
+    if (int rc = dispatch_step(f, Pin, min, frame_dt, dt, Pout, mout, varout, true, kind, forced_shift)) return rc;
     return keep ? pnmol_record_enqueue(f, Pout, mout, varout) : 0;
 }
 
@@ -3877,6 +3884,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_observe_plan_free(f);
     pnmol_record_free(f);
     pnmol_reaction_free_ws(f);
+    pnmol_forcing_free(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -3967,6 +3975,10 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
         ctx->err = "pnmol_filter_set_operator: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
         return -1;
     }
+    if (pnmol_forcing_set(f)) {
+        ctx->err = "pnmol_filter_set_operator: clear the forcing first (pnmol_filter_set_forcing(f, 0, NULL), pnmol_filter_force_at(f, NULL))";
+        return -1;
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<int> ecol;
     std::vector<double> eval;
@@ -3989,6 +4001,10 @@ int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, c
     pnmol_ctx* ctx = f->ctx;
     if (has_term(f)) {
         ctx->err = "pnmol_filter_set_operator_diagonal: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
+        return -1;
+    }
+    if (pnmol_forcing_set(f)) {
+        ctx->err = "pnmol_filter_set_operator_diagonal: clear the forcing first (pnmol_filter_set_forcing(f, 0, NULL), pnmol_filter_force_at(f, NULL))";
         return -1;
     }
     if (!f->base_has_diag) {
@@ -4042,7 +4058,10 @@ int pnmol_filter_step(pnmol_filter* f, const pnmol_state* in, double dt, pnmol_s
     pnmol_ctx* ctx = f->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     k_init_call<<<1, 64, 0, ctx->stream>>>(f->info, 1, f->ctr, f->last_ctr);
-    int rc = dispatch_step(f, in->P, in->mean, in->frame_dt, dt, out->P, out->mean, out->var, false);
+    int rc = 0;
+    const double* forced_shift = pnmol_forcing_enqueue_single(f, &rc);  // (pnmol_filter_force_at: shift - rhs, behind the linearise launch)
+    if (rc != 0) return rc;
+    rc = dispatch_step(f, in->P, in->mean, in->frame_dt, dt, out->P, out->mean, out->var, false, STEP_FULL, forced_shift);
     if (rc != 0) return rc;
     k_copy_out<<<1, 256, 0, ctx->stream>>>(f->rec, nullptr, nullptr, f->info, f->h_pin_dev, 1, f->d, f->rec_cap, nullptr, nullptr, 0, 0);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -4084,6 +4103,9 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     // a table of linearisation points: enough rows left -- or the refusal, before anything is enqueued
     rc = pnmol_linearize_begin(f, k);
     if (rc != 0) return rc;
+    // a table of right-hand sides: the same
+    rc = pnmol_forcing_begin(f, k);
+    if (rc != 0) return rc;
     // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
     std::vector<int> ob_entry;
     rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
@@ -4100,6 +4122,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
     if ((rc = pnmol_record_enqueue_cursor(f)) != 0) return rc;
     if ((rc = pnmol_linearize_enqueue_cursor(f)) != 0) return rc;
+    if ((rc = pnmol_forcing_enqueue_cursor(f)) != 0) return rc;
     if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
@@ -4218,6 +4241,7 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
     const int ob_rc = pnmol_observe_plan_collect(f, &ob_step);
     // a table of linearisation points: the call's rows are consumed, unless it failed (the cursor then stays where the call began)
     pnmol_linearize_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);
+    pnmol_forcing_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);  // (a table of right-hand sides: the same rule)
     if (ob_rc != 0) {
         const int first = stuck >= 0 && (bad < 0 || stuck < bad) ? stuck : bad;  // the first step that failed by itself
         if (first < 0 || first > ob_step) return ob_rc;                         // (ctx->err names entry, pivot and step)
@@ -4260,10 +4284,12 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
         const int ob_next = pnmol_observe_plan_cursor(f);  // (a sensor plan: the rehearsal applies entries; the cursor goes back)
         const int rec_next = pnmol_record_cursor(f);       // (a recorder: the rehearsal fills slots the real call fills again)
         const int lin_next = pnmol_linearize_cursor(f);    // (linearisation points: the rehearsal consumes rows of the real call)
+        const int frc_next = pnmol_forcing_cursor(f);      // (right-hand sides: the same)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
         pnmol_observe_plan_rewind(f, ob_next);
         pnmol_record_rewind(f, rec_next);
         pnmol_linearize_rewind(f, lin_next);
+        pnmol_forcing_rewind(f, frc_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

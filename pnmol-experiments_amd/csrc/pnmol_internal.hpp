@@ -212,6 +212,10 @@ struct pnmol_filter {
     // Linearisation points of the constant-step loop (pnmol_filter_set_linearization_points, pnmol_reaction.hip): NULL = none, every
     // step is linearised at its own predicted mean.  While a table is set the i-th step taken since is linearised at its row i.
     struct LinearizeDev* lin_plan = nullptr;
+    // Driven problems (pnmol_filter_set_forcing, pnmol_filter_force_at, pnmol_forcing.hip): NULL = none.  While a table is set the
+    // constant-step loop runs non-fused and its i-th step taken since measures against row i; a forced step reads its shift from a
+    // buffer of the forcing's own, so `shift` stays what the operator setters and the term kernels made it.
+    struct ForcingDev* forcing = nullptr;
     // Linear functionals of the trajectory (pnmol_functionals, pnmol_functional.hip): the workspace of the pass, allocated on first use
     struct FunctionalWs* fn_ws = nullptr;
 };
@@ -345,6 +349,23 @@ int pnmol_linearize_enqueue_cursor(pnmol_filter* f);
 void pnmol_linearize_collect(pnmol_filter* f, int k, bool ok);
 int pnmol_linearize_cursor(const pnmol_filter* f);
 void pnmol_linearize_rewind(pnmol_filter* f, int next);
+// pnmol_forcing.hip: the forcing inside pnmol_filter_step and pnmol_filter_steps_begin / _end.  table_set: a table of right-hand
+// sides is set (the loop then runs non-fused: the next innovation cannot be prepared before its right-hand side is in place); set: a
+// table, or a right-hand side of pnmol_filter_force_at (the operator setters then refuse).
+bool pnmol_forcing_table_set(const pnmol_filter* f);
+bool pnmol_forcing_set(const pnmol_filter* f);
+// k_force in front of a step of the loop (the row the device words name) / of pnmol_filter_step (the row of pnmol_filter_force_at), on
+// the ctx stream, behind the step's linearise launch if there is one.  Returns the shift the step measures with, NULL without a
+// table / a right-hand side (nothing is enqueued then: the step reads f->shift as ever).  *rc = -2: the launch failed.
+const double* pnmol_forcing_enqueue_loop(pnmol_filter* f, int* rc);
+const double* pnmol_forcing_enqueue_single(pnmol_filter* f, int* rc);
+// the table inside a call, as the table of linearisation points above: refusal of k steps, cursor words, collect, cursor and rewind
+int pnmol_forcing_begin(pnmol_filter* f, int k);
+int pnmol_forcing_enqueue_cursor(pnmol_filter* f);
+void pnmol_forcing_collect(pnmol_filter* f, int k, bool ok);
+int pnmol_forcing_cursor(const pnmol_filter* f);
+void pnmol_forcing_rewind(pnmol_filter* f, int next);
+void pnmol_forcing_free(pnmol_filter* f);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);
 // pnmol_hip.hip: make ell_col / ell_val at least w slots wide.  Growing frees them (ellw = 0 until the caller has filled them): the

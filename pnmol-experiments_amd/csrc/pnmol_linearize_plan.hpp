@@ -1,19 +1,16 @@
 // pnmol_linearize_plan.hpp -- host side of the table of linearisation points of the constant-step loop
 // (pnmol_filter_set_linearization_points, pnmol_reaction.hip): validation of a table, the refusals of one pnmol_filter_steps_begin
 // call, the step -> row mapping over split calls (the runt last step of a schedule arrives as a call of its own) and the cursor,
-// which a call that failed -- or a rehearsal -- puts back.  Nothing of HIP in here: tests/linearize_plan_check.cpp builds it on its
-// own under the sanitizers.
+// which a call that failed -- or a rehearsal -- puts back.  The cursor is that of every table of the loop (pnmol_cursor_plan.hpp); what
+// is refused of a table of points is said here.  Nothing of HIP in here: tests/linearize_plan_check.cpp builds it on its own under
+// the sanitizers.
 #pragma once
-#include <algorithm>
 #include <cmath>
 #include <string>
 
-struct LinearizePlan {
-    int count = 0;  // rows of the table
-    int next = 0;   // cursor: the row the next step taken is linearised at
-    bool set() const { return count > 0; }
-    int left() const { return count - next; }
-};
+#include "pnmol_cursor_plan.hpp"
+
+using LinearizePlan = CursorPlan;  // next: the row the next step taken is linearised at
 
 // "" or why the arguments of pnmol_filter_set_linearization_points are refused.  count = 0 or no table: clears (refused only
 // inside a call).  has_term / call_running: what the filter says of itself; u: (count, d) row-major.
@@ -30,26 +27,16 @@ inline std::string linearize_plan_validate(int count, const double* u, int d, bo
 }
 
 // the plan from validated arguments; the cursor goes to row 0
-inline void linearize_plan_fill(LinearizePlan* p, int count, const double* u) {
-    *p = LinearizePlan{};
-    if (count > 0 && u) p->count = count;
-}
+inline void linearize_plan_fill(LinearizePlan* p, int count, const double* u) { cursor_plan_fill(p, count, u != nullptr); }
 
 // "" or why a call of k steps is refused.  Touches nothing of the plan.
-inline std::string linearize_plan_begin(const LinearizePlan& p, int k) {
-    if (!p.set() || k <= p.left()) return "";
-    return std::to_string(k) + " step(s) asked for, " + std::to_string(p.left()) + " of " + std::to_string(p.count) +
-           " linearisation point(s) left";
-}
+inline std::string linearize_plan_begin(const LinearizePlan& p, int k) { return cursor_plan_begin(p, k, "linearisation point(s)"); }
 
 // the row step j of the running call is linearised at
-inline int linearize_plan_row(const LinearizePlan& p, int j) { return p.next + j; }
+inline int linearize_plan_row(const LinearizePlan& p, int j) { return cursor_plan_row(p, j); }
 
-// a call of k steps has been collected.  ok: its rows are consumed.  Failed: the cursor stays where the call began -- the state the
-// call leaves behind is no input for the rows that follow, and the caller who restores the state repeats the call on the same rows.
-inline void linearize_plan_collect(LinearizePlan* p, int k, bool ok) {
-    if (ok) p->next = std::min(p->count, p->next + std::max(k, 0));
-}
+// a call of k steps has been collected: its rows are consumed, unless it failed (pnmol_cursor_plan.hpp)
+inline void linearize_plan_collect(LinearizePlan* p, int k, bool ok) { cursor_plan_collect(p, k, ok); }
 
 // put the cursor back (pnmol_filter_prepare_steps rehearses a call); a value outside [0, count] is clamped
-inline void linearize_plan_rewind(LinearizePlan* p, int next) { p->next = std::max(0, std::min(p->count, next)); }
+inline void linearize_plan_rewind(LinearizePlan* p, int next) { cursor_plan_rewind(p, next); }

@@ -81,6 +81,9 @@ SYMBOLS = {
     "pnmol_filter_set_linearization_points": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p]),
     "pnmol_filter_linearization_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pnmol_filter_linearize_at": (ctypes.c_int, [_vp, _c_double_p]),
+    "pnmol_filter_set_forcing": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p]),
+    "pnmol_filter_forcing_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_filter_force_at": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
     "pnmol_state_clone": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
@@ -461,6 +464,31 @@ class Filter:
         u = _f64(u, (self.d,))
         self.ctx.check(self.lib.pnmol_filter_linearize_at(self.handle, _dp(u)), "pnmol_filter_linearize_at")
         self.error_model_dt = None
+
+    def set_forcing(self, rhs):
+        """Right-hand sides for the constant-step loop (`pnmol_filter_set_forcing`): `rhs` (count, m), a row [source (d); boundary
+        values (nB)]; the k-th step `steps` takes from now on measures against row k.  The cursor starts at row 0."""
+        r = _f64(rhs)
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != self.m:
+            raise ValueError(f"rhs must be (count, {self.m}) with count >= 1, got {r.shape} (clear_forcing() drops the table)")
+        self.ctx.check(self.lib.pnmol_filter_set_forcing(self.handle, r.shape[0], _dp(r)), "pnmol_filter_set_forcing")
+
+    def clear_forcing(self):
+        """Drop the table: the filter then takes the launches and gives the bits of one that never had a table."""
+        self.ctx.check(self.lib.pnmol_filter_set_forcing(self.handle, 0, None), "pnmol_filter_set_forcing")
+
+    def forcing_pending(self):
+        """(next, count): the table's cursor -- the row the next step measures against -- and its number of rows ((0, 0): none)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.pnmol_filter_forcing_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
+                       "pnmol_filter_forcing_pending")
+        return nxt.value, n.value
+
+    def force_at(self, rhs):
+        """The right-hand side `rhs` (m,) every `step` measures against from now on (`pnmol_filter_force_at`; no
+        synchronisation); None returns the filter to unforced."""
+        r = None if rhs is None else _f64(rhs, (self.m,))
+        self.ctx.check(self.lib.pnmol_filter_force_at(self.handle, None if r is None else _dp(r)), "pnmol_filter_force_at")
 
     def step(self, state_in, dt, want_error=True):
         out = State(self)

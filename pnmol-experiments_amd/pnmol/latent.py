@@ -59,6 +59,7 @@ class _LatentForceEK1Base(white._WhiteNoiseEK1Base):
     def initialize(self, pde):
         """Prior conditioned on y0 (nugget 1e-6), then the stack on the PDE/BC residual at t0 (nugget 1e-6)
         (latent.py:20-134), block-wise in closed form like `white._WhiteNoiseEK1Base.initialize`."""
+        self._check_forcing_supported(pde)
         self.state_iwp, self.lf_iwp, self.E0, self.E1, gamma = self.initialize_iwp_latent(pde)
         self.iwp = self.state_iwp
         self.ssm = stacked_ssm.StackedSSM(processes=[self.state_iwp, self.lf_iwp])
@@ -83,14 +84,14 @@ class _LatentForceEK1Base(white._WhiteNoiseEK1Base):
         G1 = scipy.linalg.cho_solve(S1, Kc).T
         V0 = nug2 * 0.5 * (G1 + G1.T)
         m0 = G1 @ pde.y0
-        M, shift = self._linearize(pde, m0, pde.t0)
+        M, shift, g = self._linearize_forced(pde, m0, pde.t0)
         nB = pde.B.shape[0]
         if nB > 0:                                              # boundary rows touch derivative 0 of u only
             Sb = pde.B @ V0 @ pde.B.T + nug2 * np.eye(nB)
             Gb = np.linalg.solve(Sb, pde.B @ V0).T
             # the reference updates PDE and BC rows jointly at the linearisation point m0 (latent.py:88-107);
             # the rows are conditionally independent given the state, so processing them in sequence is the same
-            m0b = m0 - Gb @ (pde.B @ m0)
+            m0b = m0 - Gb @ (pde.B @ m0 - g)
             V0 = V0 - Gb @ (pde.B @ V0)
             V0 = 0.5 * (V0 + V0.T)
         else:
@@ -135,6 +136,9 @@ class _LatentForceEK1Base(white._WhiteNoiseEK1Base):
             m_at = flt.predict_mean(dev_in, dt)                 # E0 u of the predicted mean
             M, shift = self._linearize(pde, m_at, state.t + dt)
             flt.set_operator(self._stacked_operator(M), shift)
+        forcing = getattr(pde, "forcing", None)
+        if forcing is not None:                                 # the step measures against rhs(t + dt)
+            flt.force_at(forcing.rhs(state.t + dt, pde))
         dev_out, info, _ = flt.step(dev_in, dt)
         self.last_step_info = info
         new_state = pdefilter.PDEFilterState(
@@ -157,7 +161,9 @@ class SemiLinearLatentForceEK1(_LatentForceEK1Base):
     _linearize = staticmethod(white.SemiLinearWhiteNoiseEK1._linearize)
 
     def solve_marginals(self, pde, *, num_steps=None, observations=None):
+        self._check_forcing_supported(pde)
         raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
 
     def solve_on_device(self, pde, *, num_steps=None, observations=None):
+        self._check_forcing_supported(pde)
         raise TypeError("solve_on_device keeps the loop on the device and needs a linear PDE; use solve()")

@@ -10,19 +10,21 @@ import functools
 import numpy as np
 
 from .. import diffops, discretize, kernels, mesh
+from . import forcing as _forcing
 from . import problems, reactions
 
 
 def heat_1d_discretized(*, bbox=None, dx=0.05, stencil_size_interior=3, stencil_size_boundary=3, t0=0.0, tmax=5.0,
                         y0_fun=None, diffusion_rate=0.05, nugget_gram_matrix_fd=0.0, kernel=None,
-                        bcond="dirichlet"):
+                        bcond="dirichlet", forcing=None):
+    """forcing: a `pnmol.pde.forcing.Forcing` (source s(t, x), boundary values g(t)) or None; it becomes `pde.forcing`."""
     heat = heat_1d(bbox=bbox, t0=t0, tmax=tmax, y0_fun=y0_fun, diffusion_rate=diffusion_rate, bcond=bcond)
     mesh_spatial = mesh.RectangularMesh.from_bbox_1d(heat.bbox, step=dx)
     if kernel is None:
         kernel = kernels.SquareExponential()
     heat.discretize(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
                     stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
-    return heat
+    return _forcing.attach(heat, forcing)
 
 
 def heat_1d(*, bbox=None, t0=0.0, tmax=5.0, y0_fun=None, diffusion_rate=0.05, bcond="dirichlet"):
@@ -179,10 +181,11 @@ def spruce_budworm_1d(*, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=0.1, y0_fu
 
 def reaction_diffusion_1d_discretized(reaction, *, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=1.0, y0_fun=None, dx=0.1,
                                       kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
-                                      stencil_size_boundary=3, bcond="dirichlet"):
+                                      stencil_size_boundary=3, bcond="dirichlet", forcing=None):
     """u_t = kappa u_xx + r(u) for a pointwise `reaction` (pde/reactions.py), discretised like the spruce-budworm recipe
     above: the same problem class, with f, df and df_diagonal taken from the reaction.  `pde.reaction` lets the solver
-    evaluate r on the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`)."""
+    evaluate r on the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`).  forcing: a `pnmol.pde.forcing.Forcing` or
+    None; it becomes `pde.forcing`, and `pde.f` includes its source."""
     if bbox is None:
         bbox = [0.0, 1.0]
     bbox = np.asarray(bbox, dtype=np.float64)
@@ -200,17 +203,17 @@ def reaction_diffusion_1d_discretized(reaction, *, bbox=None, t0=0.0, tmax=10.0,
         kernel = kernels.SquareExponential()
     pde.discretize(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
                    stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
-    return pde
+    return _forcing.attach(pde, forcing, f)
 
 
 def convection_diffusion_1d_discretized(term, *, bbox=None, t0=0.0, tmax=10.0, diffusion_rate=1.0, y0_fun=None, dx=0.1,
                                         kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
-                                        stencil_size_boundary=3, gradient_stencil_size=3, bcond="dirichlet"):
+                                        stencil_size_boundary=3, gradient_stencil_size=3, bcond="dirichlet", forcing=None):
     """u_t = kappa u_xx + c(u) u_x + r(u) for a convection `term` (pde/reactions.py, `Convection`), discretised like
     `reaction_diffusion_1d_discretized`.  The term's operator G is the kernel finite-difference gradient on the mesh's own
     neighbour sets (`gradient_stencil_size` points, interior and boundary rows alike); f and df come from the term, and
     `pde.reaction` lets the solver linearise on the device.  E_sqrtm stays the Laplacian's: the uncertainty of G's weights is
-    not modelled."""
+    not modelled.  forcing: as in `reaction_diffusion_1d_discretized`."""
     if bbox is None:
         bbox = [0.0, 1.0]
     bbox = np.asarray(bbox, dtype=np.float64)
@@ -232,7 +235,7 @@ def convection_diffusion_1d_discretized(term, *, bbox=None, t0=0.0, tmax=10.0, d
                                        stencil_size_interior=gradient_stencil_size,
                                        stencil_size_boundary=gradient_stencil_size, nugget_gram_matrix=nugget_gram_matrix_fd)
     term.set_operator(G)
-    return pde
+    return _forcing.attach(pde, forcing, f)
 
 
 def burgers_1d_discretized(viscosity=0.02, **kwargs):
@@ -242,11 +245,12 @@ def burgers_1d_discretized(viscosity=0.02, **kwargs):
 
 def reaction_diffusion_system_1d_discretized(reaction, *, diffusion_rates, y0_fun, bbox=None, t0=0.0, tmax=10.0, dx=0.05,
                                              kernel=None, nugget_gram_matrix_fd=0.0, stencil_size_interior=3,
-                                             stencil_size_boundary=3):
+                                             stencil_size_boundary=3, forcing=None):
     """(u_c)_t = D_c (u_c)_xx + r_c(u_0, ..., u_{C-1}) for a coupled pointwise `reaction` (pde/reactions.py, `SystemReaction`),
     Neumann boundary: the problem class and discretisation of the Lotka-Volterra / SIR recipes above, with f and df taken from
     the reaction.  `y0_fun(x)` returns the stacked initial values [u_0; ...; u_{C-1}].  `pde.reaction` lets the solver linearise on
-    the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`); the recipes above carry callables only."""
+    the device (white.py, `SemiLinearWhiteNoiseEK1.reaction_on_device`); the recipes above carry callables only.  forcing: as in
+    `reaction_diffusion_1d_discretized`; its source returns the stacked values of all species."""
     diffusion_rates = tuple(float(r) for r in diffusion_rates)
     if len(diffusion_rates) != reaction.ncomp:
         raise ValueError(f"expected {reaction.ncomp} diffusion rates, one per species, got {len(diffusion_rates)}")
@@ -264,7 +268,7 @@ def reaction_diffusion_system_1d_discretized(reaction, *, diffusion_rates, y0_fu
         kernel = kernels.SquareExponential()
     pde.discretize_system(mesh_spatial=mesh_spatial, kernel=kernel, stencil_size_interior=stencil_size_interior,
                           stencil_size_boundary=stencil_size_boundary, nugget_gram_matrix=nugget_gram_matrix_fd)
-    return pde
+    return _forcing.attach(pde, forcing, f)
 
 
 def lotka_volterra_y0(x):

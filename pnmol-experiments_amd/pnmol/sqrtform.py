@@ -35,6 +35,7 @@ class _SqrtFormMixin:
         kron(Gamma, c I), conditioned on y0 (nugget 1e-10), then on the PDE/BC residual at t0."""
         from pnmol.base import sqrt as dsqrt
 
+        self._check_forcing_supported(pde)
         self.iwp, self.E0, self.E1, gamma = self.initialize_iwp(pde)
         self._gram = gamma @ gamma.T
         self._device_pde = pde
@@ -104,6 +105,7 @@ class _SqrtFormMixin:
     def solve_marginals(self, pde, *, num_steps=None, observations=None):
         """As `pnmol.white.LinearWhiteNoiseEK1.solve_marginals`, the loop kept on the device in square-root form (which takes no
         observations: `_check_observations_supported`)."""
+        self._check_forcing_supported(pde)
         if observations is not None:
             self._check_observations_supported()
         if self.semilinear:
@@ -161,6 +163,7 @@ class _SqrtFormLatentMixin(_SqrtFormMixin):
         from pnmol.base import sqrt as dsqrt
         from pnmol.base import stacked_ssm
 
+        self._check_forcing_supported(pde)
         self.state_iwp, self.lf_iwp, self.E0, self.E1, gamma = self.initialize_iwp_latent(pde)
         self.iwp = self.state_iwp
         self.ssm = stacked_ssm.StackedSSM(processes=[self.state_iwp, self.lf_iwp])

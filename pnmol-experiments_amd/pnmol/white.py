@@ -90,6 +90,37 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         """The reaction term the device evaluates itself for this solver and problem, or None (host callables)."""
         return None
 
+    # ------------------------------------------------------------------ driven problems
+    def _check_forcing_supported(self, pde):
+        """A problem with `pde.forcing` (pde/forcing.py) is honoured or refused, never ignored: the refusal, before any device
+        work.  Returns the forcing, or None."""
+        forcing = getattr(pde, "forcing", None)
+        if forcing is None:
+            return None
+        from . import latent, sqrtform
+
+        is_latent = isinstance(self, latent._LatentForceEK1Base)
+        ok = (not isinstance(self, sqrtform._SqrtFormMixin) and self.dtype == "f64"
+              and (not self.semilinear or (not is_latent and self._reaction_for_device(pde) is not None)))
+        if not ok:
+            raise TypeError(f"pde.forcing (source / boundary values) is honoured by the fp64 covariance-form solvers "
+                            f"LinearWhiteNoiseEK1, LinearLatentForceEK1 and SemiLinearWhiteNoiseEK1 with a term the device "
+                            f"linearises (`pde.reaction`, reaction_on_device=True); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} on this problem is not one")
+        return forcing
+
+    def _linearize_forced(self, pde, m_at, t):
+        """(M, shift (d,), g (nB,)) of the measurement z = [x1 - M x0 + shift; B x0 - g] at time t: `_linearize`, with the source
+        of `pde.forcing` taken off the shift (a semilinear `_linearize` has done so: `pde.f` includes the source) and its boundary
+        values."""
+        M, shift = self._linearize(pde, m_at, t)
+        forcing = getattr(pde, "forcing", None)
+        if forcing is None:
+            return M, shift, np.zeros(pde.B.shape[0])
+        if not self.semilinear:
+            shift = shift - forcing.source_values(t, pde)
+        return M, shift, forcing.boundary(t, pde)
+
     # True: the reference's own two `update_sqrt` calls, on the device (below); False: closed form on the host (O(d^3) LAPACK);
     # None (default; PNMOL_INIT_ON_DEVICE=0/1 overrides): on the device from n d >= 4096 on, where the host form takes
     # seconds (64x64 mesh: 18 s against 10 s), closed form below that (its rounding-level entries are what the
@@ -110,12 +141,12 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             C0_raw[a::n, a::n] = self.diffuse_prior_scale * gamma
         C0_y0, k_y0, _ = dsqrt.update_sqrt(self.E0, C0_raw, 1e-10 * np.eye(d), ctx=ctx)
         m0_y0 = k_y0 @ pde.y0
-        M, shift = self._linearize(pde, m0_y0[0::n], pde.t0)
+        M, shift, g = self._linearize_forced(pde, m0_y0[0::n], pde.t0)
         H = np.zeros((d + nB, n * d))
         H[:d, 0::n] = -M
         H[np.arange(d), np.arange(d) * n + 1] += 1.0
         H[d:, 0::n] = pde.B
-        z = H @ m0_y0 + np.concatenate([shift, np.zeros(nB)])
+        z = H @ m0_y0 + np.concatenate([shift, -g])
         E = np.zeros((d + nB, d + nB))
         E[:d, :d], E[d:, d:] = pde.E_sqrtm, pde.R_sqrtm
         C0, k, _ = dsqrt.update_sqrt(H, C0_y0, E + 1e-10 * np.eye(d + nB), ctx=ctx)
@@ -130,8 +161,10 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         The two updates of the reference have observation noise ~1e-20, which a plain covariance
         update cannot resolve; here they are evaluated block-wise in closed form (the prior
         Gamma Gamma^T (x) c^2 I is Kronecker, the derivative blocks decouple), every difference
-        written so that it does not cancel.  O(d^3) on the host, once per solve.
+        written so that it does not cancel.  O(d^3) on the host, once per solve.  A driven problem (`pde.forcing`): the update
+        at t0 measures against rhs(t0).
         """
+        self._check_forcing_supported(pde)
         self.iwp, self.E0, self.E1, gamma = self.initialize_iwp(pde)
         self._bind(pde, gamma)
         n, d = self.num_derivatives + 1, pde.L.shape[0]
@@ -161,7 +194,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         V0 = eps2 * 0.5 * (G1 + G1.T)
         m0 = G1 @ pde.y0
         # update 2 (white.py:42-58): rows [E1 - M E0 ; B E0], noise (E_bc + 1e-10 I)(...)^T, block diagonal
-        M, shift = self._linearize(pde, m0, pde.t0)
+        M, shift, g = self._linearize_forced(pde, m0, pde.t0)
         nB = pde.B.shape[0]
         En = pde.E_sqrtm + 1e-10 * np.eye(d)
         Rn = pde.R_sqrtm + 1e-10 * np.eye(nB)
@@ -170,7 +203,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         if nB > 0:
             Sb = pde.B @ V0 @ pde.B.T + Rb
             Gb = np.linalg.solve(Sb, pde.B @ V0).T              # V0 B^T Sb^-1
-            m0 = m0 - Gb @ (pde.B @ m0)
+            m0 = m0 - Gb @ (pde.B @ m0 - g)
             V0 = V0 - Gb @ (pde.B @ V0)
             V0 = 0.5 * (V0 + V0.T)
         # (b) PDE rows: z = x1 - M x0 + shift, prior blockdiag(V0, Kc);  Sp = Kc + T, T tiny
@@ -274,6 +307,9 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                     flt.prepare_error_model(dt)
         else:
             self._ensure_error_model(pde, dt)
+        forcing = getattr(pde, "forcing", None)
+        if forcing is not None:                                 # behind the linearisation: the step measures against rhs(t + dt)
+            self._device_filter.force_at(forcing.rhs(state.t + dt, pde))
         dev_out, info, error = self._device_filter.step(dev_in, dt)
         self.last_step_info = info
         m_new = dev_out.mean()
@@ -349,19 +385,33 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         """
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_marginals needs the Constant step rule")
+        self._check_forcing_supported(pde)
         if observations is not None:
             return self._solve_marginals_observed(pde, num_steps, observations, linearize_at)
         ts, dts = self._constant_schedule(pde, num_steps)
         pts = self._checked_linearization_points(pde, linearize_at, len(dts))
+        rhs = self._forcing_table(pde, ts)
         state = self.initialize(pde)
-        if pts is None or not dts:
+        if (pts is None and rhs is None) or not dts:
             return self._run_device_loop(pde, state, ts, dts)
         flt = self._device_filter
         try:
-            flt.set_linearization_points(pts)
+            if pts is not None:
+                flt.set_linearization_points(pts)
+            if rhs is not None:
+                flt.set_forcing(rhs)
             return self._run_device_loop(pde, state, ts, dts)
         finally:
-            self._clear_quietly(flt.clear_linearization_points)
+            self._clear_quietly(flt.clear_linearization_points if pts is not None else None,
+                                flt.clear_forcing if rhs is not None else None)
+
+    def _forcing_table(self, pde, ts):
+        """The right-hand sides of the constant schedule `ts` (a runt last step included) as the (T, m) table the device takes, or
+        None: no `pde.forcing`, or no step.  Validated on the host, in front of any device work."""
+        forcing = self._check_forcing_supported(pde)
+        if forcing is None or len(ts) < 2:
+            return None
+        return np.ascontiguousarray(forcing.table(ts, pde))
 
     def _constant_schedule(self, pde, num_steps):
         """(times, steps) of the constant-step loop: the t-accumulation of the reference, a runt final step included."""
@@ -408,6 +458,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         dt0 = self.steprule.first_dt(pde)
         ts, dts = self._constant_schedule(pde, num_steps)
         pts = self._checked_linearization_points(pde, linearize_at, len(dts))
+        rhs = self._forcing_table(pde, ts)
         if obs:
             times, C, R, ys = data.shared_sensors(obs)
             if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
@@ -425,6 +476,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 flt.set_observations(times, Cd, ys, R)
             if pts is not None and dts:
                 flt.set_linearization_points(pts)
+            if rhs is not None:
+                flt.set_forcing(rhs)
             out = self._run_device_loop(pde, state, ts, dts)
             applied, nobs = flt.observations_pending()
             if applied != nobs:
@@ -435,11 +488,14 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 flt.clear_observations()
             except _hip.PnmolHipError:
                 pass
-            self._clear_quietly(flt.clear_linearization_points if pts is not None else None)
+            self._clear_quietly(flt.clear_linearization_points if pts is not None else None,
+                                flt.clear_forcing if rhs is not None else None)
             raise
         flt.clear_observations()
         if pts is not None:
             flt.clear_linearization_points()
+        if rhs is not None:
+            flt.clear_forcing()
         info = dict(num_steps=len(dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
         return out + (info,)
 
@@ -459,6 +515,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_on_device needs the Constant step rule")
+        self._check_forcing_supported(pde)
         if isinstance(self, sqrtform._SqrtFormMixin) or self.dtype != "f64":
             raise TypeError(f"solve_on_device() supports the fp64 covariance-form solvers of pnmol.white and pnmol.latent; "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
@@ -468,6 +525,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
         ts, dts = self._constant_schedule(pde, num_steps)
         pts = self._checked_linearization_points(pde, linearize_at, len(dts))
+        rhs = self._forcing_table(pde, ts)
         if obs:
             times, C, R, ys = data.shared_sensors(obs)
             if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
@@ -492,6 +550,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 flt.set_recorder(slots)
                 if pts is not None:
                     flt.set_linearization_points(pts)
+                if rhs is not None:
+                    flt.set_forcing(rhs)
                 # (the loop advances its state in place: it works on a copy, the initial state stays what `ys[0]` holds)
                 work = state._replace(y=rv.DeviceMultivariateNormal(first.mean, first.device_state.clone()))
                 _, _, _, sig, _ = self._run_device_loop(pde, work, ts, dts)
@@ -500,6 +560,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                     raise RuntimeError(f"{count - filled} step(s) of the loop were not recorded")
                 if pts is not None and flt.linearization_pending() != (len(dts), len(dts)):
                     raise RuntimeError("the loop did not consume every linearisation point")
+                if rhs is not None and flt.forcing_pending() != (len(dts), len(dts)):
+                    raise RuntimeError("the loop did not consume every right-hand side of the forcing")
                 means = flt.recorder_means(0, count)            # one read-back for all states
             else:
                 means = np.zeros((0,) + first.mean.shape)
@@ -510,7 +572,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
         finally:
             for clear in (flt.clear_recorder, flt.clear_observations if planned else None,
-                          flt.clear_linearization_points if pts is not None else None):
+                          flt.clear_linearization_points if pts is not None else None,
+                          flt.clear_forcing if rhs is not None else None):
                 try:                                            # (a failure above is the one to report, not one of the clear)
                     if clear is not None:
                         clear()
@@ -558,6 +621,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_iterated needs the Constant step rule")
+        self._check_forcing_supported(pde)
         if (not isinstance(self, SemiLinearWhiteNoiseEK1) or isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin))
                 or self.dtype != "f64" or self._reaction_for_device(pde) is None):
             raise TypeError(f"solve_iterated() supports pnmol.white.SemiLinearWhiteNoiseEK1 in the fp64 covariance form on a problem "
@@ -773,7 +837,11 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
         if isinstance(term, Convection) and pde.L.shape[0] == pde.L.shape[1]:
             # the structured host form (operator entries and shift in the device's order of operations, no dense J_x @ m):
             # the host route and the device route then produce the same operator and shift
-            return term.linearization(m_at, L=pde.L)
+            M, shift = term.linearization(m_at, L=pde.L)
+            forcing = getattr(pde, "forcing", None)             # (every other branch reads the source through `pde.f`)
+            if forcing is not None:
+                shift = shift - forcing.source_values(t, pde)
+            return M, shift
         fx = np.asarray(pde.f(t, m_at), dtype=np.float64)
         Jx = np.asarray(pde.df(t, m_at), dtype=np.float64)
         return pde.L + Jx, Jx @ m_at - fx
@@ -803,11 +871,13 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
         return reaction
 
     def solve_marginals(self, pde, *, num_steps=None, observations=None, linearize_at=None):
+        self._check_forcing_supported(pde)
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
         return super().solve_marginals(pde, num_steps=num_steps, observations=observations, linearize_at=linearize_at)
 
     def solve_on_device(self, pde, *, num_steps=None, observations=None, linearize_at=None):
+        self._check_forcing_supported(pde)
         if self._reaction_for_device(pde) is None:
             raise TypeError("solve_on_device keeps the loop on the device and needs a linear PDE; use solve()")
         return super().solve_on_device(pde, num_steps=num_steps, observations=observations, linearize_at=linearize_at)
