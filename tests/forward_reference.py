@@ -226,25 +226,33 @@ def _solve_upper_ld(U, b):
 
 
 # ---- extended-precision truth ---------------------------------------------------------------------------------------------
-def error_model_truth(case, op):
-    """(Sq, diag Sq) of `estimate_error` for the operator, longdouble: Sq = H Q H^T + E E^T in the frame of h."""
-    if op._error_model is None:
-        HQ = h_apply(case, op, case.Qx)
-        Sq = h_apply(case, op, np.ascontiguousarray(HQ.T)) + case.EEtx
-        op._error_model = 0.5 * (Sq + Sq.T)
-    return op._error_model
+def error_model_truth(case, op, Qx=None, EEtx=None):
+    """(Sq, diag Sq) of `estimate_error` for the operator, longdouble: Sq = H Q H^T + E E^T in the frame of h.  With the case's
+    own Q and E E^T it is kept on the operator; with another process noise or measurement covariance (tests/sqrt_reference.py,
+    which keeps its own per case and operator) it is computed and returned."""
+    if Qx is None and EEtx is None:
+        if op._error_model is None:
+            HQ = h_apply(case, op, case.Qx)
+            Sq = h_apply(case, op, np.ascontiguousarray(HQ.T)) + case.EEtx
+            op._error_model = 0.5 * (Sq + Sq.T)
+        return op._error_model
+    HQ = h_apply(case, op, case.Qx if Qx is None else Qx)
+    Sq = h_apply(case, op, np.ascontiguousarray(HQ.T)) + (case.EEtx if EEtx is None else EEtx)
+    return 0.5 * (Sq + Sq.T)
 
 
-def step_truth_frame(case, mh, Ph, op=None):
-    """One step from the state (mh (D,), Ph (D, D)) given in the frame of h, longdouble."""
+def step_truth_frame(case, mh, Ph, op=None, Qx=None, EEtx=None, Sq=None):
+    """One step from the state (mh (D,), Ph (D, D)) given in the frame of h, longdouble.  Qx, EEtx: the process noise and the
+    measurement covariance E E^T of the model (default: the case's); Sq: `error_model_truth` of that model, where the caller
+    has it already."""
     op = op or case.base
     mrows = case.m
     mm = kron_left(case.A1x, mh)
-    Pm = kron_right(kron_left(case.A1x, Ph), case.A1x) + case.Qx
+    Pm = kron_right(kron_left(case.A1x, Ph), case.A1x) + (case.Qx if Qx is None else Qx)
     Pm = 0.5 * (Pm + Pm.T)
     HP = h_apply(case, op, Pm)                                                   # (m, D)
     z = h_apply(case, op, mm) + op.zshift.astype(LD)
-    S = h_apply(case, op, np.ascontiguousarray(HP.T)) + case.EEtx
+    S = h_apply(case, op, np.ascontiguousarray(HP.T)) + (case.EEtx if EEtx is None else EEtx)
     S = 0.5 * (S + S.T)
     X = _solve_refined(S, HP)
     v = _solve_refined(S, z)
@@ -252,7 +260,7 @@ def step_truth_frame(case, mh, Ph, op=None):
     m = mm - HP.T @ v
     Ls = cholesky_ld(S)
     r = _solve_upper_ld(Ls.T, z)                                                 # Ls^-T z: quirk Q1
-    Sq = error_model_truth(case, op)
+    Sq = error_model_truth(case, op, Qx, EEtx) if Sq is None else Sq
     vq = _solve_refined(Sq, z)
     err_sigma2 = z @ vq / mrows
     return types.SimpleNamespace(mm=mm, Pm=Pm, z=z, S=S, m=m, P=0.5 * (P + P.T), sigma2_whitened=z @ v / mrows,
