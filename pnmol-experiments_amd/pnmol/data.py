@@ -8,6 +8,8 @@ give the posterior under physics and data, and `info["data_log_likelihood"]` is 
 No reference counterpart: the reference solves the PDE without data.
 """
 
+import itertools
+
 import numpy as np
 
 _EPS = 2.220446049250313e-16
@@ -78,14 +80,27 @@ class Observation:
         return f"Observation(t={self.t}, q={self.q}, noise={'none' if self.R_sqrtm is None else 'given'})"
 
 
-def constant_step_grid(t0, tmax, dt0):
-    """The times of the constant-step loop (pdefilter.py:140-160 of the reference, including a runt final step)."""
-    ts, t, dt = [t0], t0, dt0
-    while t < tmax:
+def constant_schedule(t0, tmax, dt0, num_steps=None):
+    """(times, steps) of the constant-step loop, as lists: the t-accumulation of the reference's loop (pdefilter.py:140-160,
+    :220-223), a runt final step included when sum(dt) lands short of tmax; at most `num_steps` steps."""
+    ts, dts, t, dt = [t0], [], t0, dt0
+    while t < tmax and (num_steps is None or len(dts) < num_steps):
+        dts.append(dt)
         t = t + dt
         ts.append(t)
         dt = min(dt0, tmax - t)
-    return np.array(ts)
+    return ts, dts
+
+
+def constant_step_grid(t0, tmax, dt0):
+    """The times of the constant-step loop (`constant_schedule`) as an array."""
+    return np.array(constant_schedule(t0, tmax, dt0)[0])
+
+
+def equal_step_runs(dts):
+    """(count, dt) per run of equal steps in `dts`: what the device loops take in one call each."""
+    for dt, run in itertools.groupby(dts):
+        yield sum(1 for _ in run), dt
 
 
 def prepare(observations, pde, steprule, d):

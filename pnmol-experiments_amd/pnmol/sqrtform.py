@@ -19,12 +19,13 @@ import numpy as np
 
 import scipy.linalg
 
-from pnmol import _hip, latent, pdefilter, white
+from pnmol import _hip, data, latent, pdefilter, white
 from pnmol.base import rv
 from pnmol.odetools import step as _step
 
 
 class _SqrtFormMixin:
+    _covariance_form = False   # (`white._WhiteNoiseEK1Base._is_fp64_covariance_form`)
     _sqrt_filter = None
     _sqrt_last = None      # the state object whose factor is resident in the device filter
 
@@ -112,25 +113,15 @@ class _SqrtFormMixin:
             raise TypeError("solve_marginals keeps the loop on the device and needs a linear PDE; use solve()")
         state = self.initialize(pde)
         self._load(state, pde)
-        flt, dt0 = self._sqrt_filter, self.steprule.first_dt(pde)
-        ts, dts, t, dt = [pde.t0], [], pde.t0, dt0
-        while t < pde.tmax and (num_steps is None or len(dts) < num_steps):
-            dts.append(dt)
-            t = t + dt
-            ts.append(t)
-            dt = min(dt0, pde.tmax - t)
+        flt = self._sqrt_filter
+        ts, dts = self._constant_schedule(pde, num_steps)
         C0 = np.asarray(state.y.cov_sqrtm)
         d = pde.L.shape[0]                         # (the latent-force state carries eps behind u)
         means, stds, sig = [state.y.mean[0][:d]], [np.sqrt(np.einsum("ij,ij->i", C0, C0)[:: self.num_derivatives + 1][:d])], []
-        i = 0
-        while i < len(dts):
-            j = i
-            while j < len(dts) and dts[j] == dts[i]:
-                j += 1
-            mk, sk, infos = flt.steps(j - i, dts[i])
+        for count, dt in data.equal_step_runs(dts):
+            mk, sk, infos = flt.steps(count, dt)
             means.extend(mk[:, :d]), stds.extend(sk[:, :d])
             sig.extend(o.diffusion_squared_local for o in infos)
-            i = j
         _, mean, C = flt.get_state()
         final = pdefilter.PDEFilterState(t=ts[-1], y=rv.MultivariateNormal(mean, C), error_estimate=None,
                                          reference_state=self._reference_state(mean), diffusion_squared_local=sig[-1] if sig else [])

@@ -14,13 +14,14 @@ Documented deviations from the reference's numbers:
 """
 
 import collections
+import contextlib
 import os
 
 import numpy as np
 import scipy.linalg
 import scipy.sparse
 
-from . import _hip, pdefilter
+from . import _hip, data, pdefilter
 from .base import iwp, rv
 from .odetools import step as _step
 
@@ -31,12 +32,29 @@ IteratedSolution.__doc__ = """Result of `solve_iterated`: the last pass's filter
 the `smooth()` solution of the last pass (or None), the relative increment of every pass beyond pass 0, their number, whether the
 last increment met the tolerance, and with observations the data log-likelihoods of the last pass (else None)."""
 
+_LoopPlan = collections.namedtuple("_LoopPlan", "ts dts points forcing observations sensors at_t0")
+_LoopPlan.__doc__ = """What one run of the device-resident constant-step loop needs, validated on the host (`_loop_plan`): the schedule
+`ts` / `dts`; per option its table or None -- `points` (T, d) to linearise at, `forcing` (T, m) right-hand sides --; `observations` as
+`data.prepare` returns them (None: the caller gave none); `sensors` = (times, C, R_sqrtm, ys) of the shared sensor array for the
+observations behind t0 (None: there are none); `at_t0`: whether `observations[0]` sits at t0 and updates the initial state."""
+
+
+def _padded_to_state(C, ds):
+    """C with zero columns up to the state width `ds` of the bound filter (the eps half of a latent-force state)."""
+    return C if C.shape[1] == ds else np.hstack((C, np.zeros((C.shape[0], ds - C.shape[1]))))
+
 
 class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
     _device_filter = None
     _device_pde = None
     _error_models = None
     last_step_info = None
+    _covariance_form = True     # (pnmol.sqrtform: False)
+
+    def _is_fp64_covariance_form(self):
+        """This solver advances an fp64 covariance: `pnmol.white` / `pnmol.latent` with dtype "f64", not `pnmol.sqrtform`.  What the
+        loop's options, the recorder, the device's own linearisation and the backward walks need."""
+        return self._covariance_form and self.dtype == "f64"
 
     # ------------------------------------------------------------------ cold path
     def initialize_iwp(self, pde):
@@ -97,10 +115,10 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         forcing = getattr(pde, "forcing", None)
         if forcing is None:
             return None
-        from . import latent, sqrtform
+        from . import latent
 
         is_latent = isinstance(self, latent._LatentForceEK1Base)
-        ok = (not isinstance(self, sqrtform._SqrtFormMixin) and self.dtype == "f64"
+        ok = (self._is_fp64_covariance_form()
               and (not self.semilinear or (not is_latent and self._reaction_for_device(pde) is not None)))
         if not ok:
             raise TypeError(f"pde.forcing (source / boundary values) is honoured by the fp64 covariance-form solvers "
@@ -320,9 +338,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
     # ------------------------------------------------------------------ sensor data
     def _check_observations_supported(self):
-        from . import sqrtform
-
-        if isinstance(self, sqrtform._SqrtFormMixin) or self.dtype != "f64":
+        if not self._is_fp64_covariance_form():
             raise TypeError(f"observations are supported by the fp64 covariance-form solvers of pnmol.white and pnmol.latent; "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
 
@@ -332,10 +348,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         latent-force state gets zero columns.  `diffusion_squared_local` keeps its meaning (PDE residuals only)."""
         flt = self._device_filter
         dev_in = self._device_state_of(state, self._device_pde)
-        C = observation.C
-        if C.shape[1] != flt.ds:
-            C = np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
-        dev_out, res = flt.observe(dev_in, C, observation.y, observation.R_sqrtm)
+        dev_out, res = flt.observe(dev_in, _padded_to_state(observation.C, flt.ds), observation.y, observation.R_sqrtm)
         m_new = dev_out.mean()
         ref = None if state.reference_state is None else np.abs(m_new[0][:observation.C.shape[1]])
         return state._replace(y=rv.DeviceMultivariateNormal(m_new, dev_out), reference_state=ref), res.log_likelihood
@@ -356,14 +369,89 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             raise ValueError("linearize_at has entries that are not finite")
         return pts
 
-    def _clear_quietly(self, *clears):
-        """The loop's options off again behind a solve; a failure of the solve is the one to report, not one of a clear."""
-        for clear in clears:
-            try:
-                if clear is not None:
-                    clear()
-            except _hip.PnmolHipError:
-                pass
+    # ------------------------------------------------------------------ the device loop and its options
+    def _loop_plan(self, pde, num_steps, observations, linearize_at):
+        """The `_LoopPlan` of a constant-step solve: every argument validated on the host, in front of `initialize`, which binds the
+        device."""
+        obs = None
+        if observations is not None:
+            self._check_observations_supported()
+            obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
+        ts, dts = self._constant_schedule(pde, num_steps)
+        points = self._checked_linearization_points(pde, linearize_at, len(dts))
+        forcing = self._forcing_table(pde, ts)
+        sensors, at_t0 = None, False
+        if obs:
+            dt0 = self.steprule.first_dt(pde)
+            times, C, R, ys = data.shared_sensors(obs)
+            if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
+                raise ValueError(f"observation at t={times[-1]} lies behind the last step taken (t={ts[-1]}, {len(dts)} steps)")
+            at_t0 = bool(data.times_agree(obs[0].t, pde.t0, dt0))   # that one updates the initial state, as solve() does it
+            if times.size > at_t0:
+                sensors = (times[at_t0:], C, R, ys[at_t0:])
+        return _LoopPlan(ts, dts, points, forcing, obs, sensors, at_t0)
+
+    def _observe_at_t0(self, state, plan):
+        """(`state` conditioned on the observation at t0, [its log-likelihood]); (`state`, []) where the plan has none there."""
+        if not plan.at_t0:
+            return state, []
+        state, ll = self._observe(state, plan.observations[0])
+        return state, [ll]
+
+    @contextlib.contextmanager
+    def _loop_options(self, flt, plan, slots=None):
+        """The options of `plan`, and the recorder into `slots`, installed on `flt` around the loop -- only where there is a step
+        to take -- and cleared behind it; yields the names of those installed.  An option is cleared once its setter was attempted
+        (one that failed half-way included), recorder first.  Behind a failure of the loop a `PnmolHipError` of a clear is dropped:
+        the failure is the one to report.  Otherwise every clear is still attempted and the first such error raised."""
+        options = {}                                            # name -> (setter, clear), in install order
+        if plan.dts:
+            if plan.sensors is not None:
+                times, C, R, ys = plan.sensors
+                options["observations"] = (lambda: flt.set_observations(times, _padded_to_state(C, flt.ds), ys, R),
+                                           flt.clear_observations)
+            if slots is not None:
+                options["recorder"] = (lambda: flt.set_recorder(slots), flt.clear_recorder)
+            if plan.points is not None:
+                options["points"] = (lambda: flt.set_linearization_points(plan.points), flt.clear_linearization_points)
+            if plan.forcing is not None:
+                options["forcing"] = (lambda: flt.set_forcing(plan.forcing), flt.clear_forcing)
+        attempted, failed = [], True
+        try:
+            for name, (install, _) in options.items():
+                attempted.append(name)
+                install()
+            yield tuple(options)
+            failed = False
+        finally:
+            errors = []
+            for name in ("recorder", "observations", "points", "forcing"):
+                try:
+                    if name in attempted:
+                        options[name][1]()
+                except _hip.PnmolHipError as error:
+                    errors.append(error)
+            if errors and not failed:
+                raise errors[0]
+
+    def _loop_consumed(self, flt, plan, installed, lls):
+        """Behind the loop, inside `_loop_options`: every installed option was used up, or RuntimeError.  Returns the data
+        log-likelihoods: `lls` (the update at t0) and those of the loop's updates."""
+        T = len(plan.dts)
+        if "recorder" in installed:
+            filled, count = flt.recorder_pending()
+            if filled != count:
+                raise RuntimeError(f"{count - filled} step(s) of the loop were not recorded")
+        if "observations" in installed:
+            applied, nobs = flt.observations_pending()
+            if applied != nobs:
+                raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
+            lls = lls + [r.log_likelihood for r in flt.observation_results(0, nobs)]
+        if "points" in installed and flt.linearization_pending() != (T, T):
+            raise RuntimeError("the loop did not consume every linearisation point")
+        if "forcing" in installed and flt.forcing_pending() != (T, T):
+            raise RuntimeError("the loop did not consume every right-hand side of the forcing")
+        return lls
 
     def solve_marginals(self, pde, *, num_steps=None, observations=None, linearize_at=None):
         """Constant-step solve that keeps everything on the device: returns
@@ -386,24 +474,15 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_marginals needs the Constant step rule")
         self._check_forcing_supported(pde)
-        if observations is not None:
-            return self._solve_marginals_observed(pde, num_steps, observations, linearize_at)
-        ts, dts = self._constant_schedule(pde, num_steps)
-        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
-        rhs = self._forcing_table(pde, ts)
-        state = self.initialize(pde)
-        if (pts is None and rhs is None) or not dts:
-            return self._run_device_loop(pde, state, ts, dts)
+        plan = self._loop_plan(pde, num_steps, observations, linearize_at)
+        state, lls = self._observe_at_t0(self.initialize(pde), plan)
         flt = self._device_filter
-        try:
-            if pts is not None:
-                flt.set_linearization_points(pts)
-            if rhs is not None:
-                flt.set_forcing(rhs)
-            return self._run_device_loop(pde, state, ts, dts)
-        finally:
-            self._clear_quietly(flt.clear_linearization_points if pts is not None else None,
-                                flt.clear_forcing if rhs is not None else None)
+        with self._loop_options(flt, plan) as installed:
+            out = self._run_device_loop(pde, state, plan.ts, plan.dts)
+            lls = self._loop_consumed(flt, plan, installed, lls)
+        if observations is None:
+            return out
+        return out + (dict(num_steps=len(plan.dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls),)
 
     def _forcing_table(self, pde, ts):
         """The right-hand sides of the constant schedule `ts` (a runt last step included) as the (T, m) table the device takes, or
@@ -415,14 +494,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
     def _constant_schedule(self, pde, num_steps):
         """(times, steps) of the constant-step loop: the t-accumulation of the reference, a runt final step included."""
-        dt0 = self.steprule.first_dt(pde)
-        ts, dts, t, dt = [pde.t0], [], pde.t0, dt0
-        while t < pde.tmax and (num_steps is None or len(dts) < num_steps):
-            dts.append(dt)
-            t = t + dt
-            ts.append(t)
-            dt = min(dt0, pde.tmax - t)
-        return ts, dts
+        return data.constant_schedule(pde.t0, pde.tmax, self.steprule.first_dt(pde), num_steps)
 
     def _run_device_loop(self, pde, state, ts, dts):
         """The steps `dts` from `state` on the device, runs of equal dt in one call each: the 5-tuple of `solve_marginals`."""
@@ -432,72 +504,17 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         means = [state.y.mean[0][:d]]
         stds = [np.sqrt(np.maximum(state.y.marginal_var[0][:d], 0.0))]
         sig = []
-        i = 0
-        while i < len(dts):                                     # runs of equal dt -> one device call each
-            j = i
-            while j < len(dts) and dts[j] == dts[i]:
-                j += 1
+        for count, dt in data.equal_step_runs(dts):             # runs of equal dt -> one device call each
             if not on_device:
-                self._ensure_error_model(pde, dts[i])
-            mk, sk, infos = self._device_filter.steps(dev, j - i, dts[i])
+                self._ensure_error_model(pde, dt)
+            mk, sk, infos = self._device_filter.steps(dev, count, dt)
             means.extend(mk), stds.extend(sk)
             sig.extend(o.diffusion_squared_local for o in infos)
-            i = j
         m_final = dev.mean()
         final = pdefilter.PDEFilterState(t=ts[-1], y=rv.DeviceMultivariateNormal(m_final, dev), error_estimate=None,
                                          reference_state=np.abs(m_final[0][:d]),
                                          diffusion_squared_local=sig[-1] if sig else [])
         return np.array(ts), np.array(means), np.array(stds), np.array(sig), final
-
-    def _solve_marginals_observed(self, pde, num_steps, observations, linearize_at=None):
-        """`solve_marginals` with sensor data: everything is validated on the host before `initialize` binds the device."""
-        from . import data
-
-        self._check_observations_supported()
-        obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
-        dt0 = self.steprule.first_dt(pde)
-        ts, dts = self._constant_schedule(pde, num_steps)
-        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
-        rhs = self._forcing_table(pde, ts)
-        if obs:
-            times, C, R, ys = data.shared_sensors(obs)
-            if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
-                raise ValueError(f"observation at t={times[-1]} lies behind the last step taken (t={ts[-1]}, {len(dts)} steps)")
-        state = self.initialize(pde)
-        flt = self._device_filter
-        lls = []
-        if obs and data.times_agree(obs[0].t, pde.t0, dt0):     # at t0: the initial state, as solve() does it
-            state, ll = self._observe(state, obs[0])
-            lls.append(ll)
-            times, ys = times[1:], ys[1:]
-        try:
-            if obs and times.size:
-                Cd = C if C.shape[1] == flt.ds else np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
-                flt.set_observations(times, Cd, ys, R)
-            if pts is not None and dts:
-                flt.set_linearization_points(pts)
-            if rhs is not None:
-                flt.set_forcing(rhs)
-            out = self._run_device_loop(pde, state, ts, dts)
-            applied, nobs = flt.observations_pending()
-            if applied != nobs:
-                raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
-            lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
-        except BaseException:
-            try:                                                # (the failure above is the one to report, not one of the clear)
-                flt.clear_observations()
-            except _hip.PnmolHipError:
-                pass
-            self._clear_quietly(flt.clear_linearization_points if pts is not None else None,
-                                flt.clear_forcing if rhs is not None else None)
-            raise
-        flt.clear_observations()
-        if pts is not None:
-            flt.clear_linearization_points()
-        if rhs is not None:
-            flt.clear_forcing()
-        info = dict(num_steps=len(dts), data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
-        return out + (info,)
 
     # ------------------------------------------------------------------ the device loop with the trajectory kept
     def solve_on_device(self, pde, *, num_steps=None, observations=None, linearize_at=None):
@@ -511,79 +528,29 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         section 20): no host round trip per step, one read-back of all means per run of equal steps.  It accepts what
         `solve_marginals` accepts (linear problems, problems whose term the device linearises, one sensor array) in the fp64
         covariance form; memory: T + 1 states of (n d)^2 doubles on the device.  linearize_at: as in `solve_marginals`."""
-        from . import data, sqrtform
-
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_on_device needs the Constant step rule")
         self._check_forcing_supported(pde)
-        if isinstance(self, sqrtform._SqrtFormMixin) or self.dtype != "f64":
+        if not self._is_fp64_covariance_form():
             raise TypeError(f"solve_on_device() supports the fp64 covariance-form solvers of pnmol.white and pnmol.latent; "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
-        obs, dt0 = None, self.steprule.first_dt(pde)
-        if observations is not None:                            # everything is validated before `initialize` binds the device
-            self._check_observations_supported()
-            obs = data.prepare(observations, pde, self.steprule, pde.y0.shape[0])
-        ts, dts = self._constant_schedule(pde, num_steps)
-        pts = self._checked_linearization_points(pde, linearize_at, len(dts))
-        rhs = self._forcing_table(pde, ts)
-        if obs:
-            times, C, R, ys = data.shared_sensors(obs)
-            if times[-1] > ts[-1] and not data.times_agree(times[-1], ts[-1], dt0):
-                raise ValueError(f"observation at t={times[-1]} lies behind the last step taken (t={ts[-1]}, {len(dts)} steps)")
-        state = self.initialize(pde)
+        plan = self._loop_plan(pde, num_steps, observations, linearize_at)
+        state, lls = self._observe_at_t0(self.initialize(pde), plan)
         flt = self._device_filter
-        lls = []
-        if obs and data.times_agree(obs[0].t, pde.t0, dt0):     # at t0: the initial state, as solve() does it
-            state, ll = self._observe(state, obs[0])
-            lls.append(ll)
-            times, ys = times[1:], ys[1:]
         first = state.y
-        slots = [flt.new_state() for _ in dts]
-        planned = False
-        try:
-            if obs and times.size:
-                Cd = C if C.shape[1] == flt.ds else np.hstack((C, np.zeros((C.shape[0], flt.ds - C.shape[1]))))
-                flt.set_observations(times, Cd, ys, R)
-                planned = True
-            sig = np.zeros(0)
-            if slots:
-                flt.set_recorder(slots)
-                if pts is not None:
-                    flt.set_linearization_points(pts)
-                if rhs is not None:
-                    flt.set_forcing(rhs)
-                # (the loop advances its state in place: it works on a copy, the initial state stays what `ys[0]` holds)
-                work = state._replace(y=rv.DeviceMultivariateNormal(first.mean, first.device_state.clone()))
-                _, _, _, sig, _ = self._run_device_loop(pde, work, ts, dts)
-                filled, count = flt.recorder_pending()
-                if filled != count:
-                    raise RuntimeError(f"{count - filled} step(s) of the loop were not recorded")
-                if pts is not None and flt.linearization_pending() != (len(dts), len(dts)):
-                    raise RuntimeError("the loop did not consume every linearisation point")
-                if rhs is not None and flt.forcing_pending() != (len(dts), len(dts)):
-                    raise RuntimeError("the loop did not consume every right-hand side of the forcing")
-                means = flt.recorder_means(0, count)            # one read-back for all states
-            else:
-                means = np.zeros((0,) + first.mean.shape)
-            if planned:
-                applied, nobs = flt.observations_pending()
-                if applied != nobs:
-                    raise RuntimeError(f"{nobs - applied} observation(s) were not reached by the loop")
-                lls.extend(r.log_likelihood for r in flt.observation_results(0, nobs))
-        finally:
-            for clear in (flt.clear_recorder, flt.clear_observations if planned else None,
-                          flt.clear_linearization_points if pts is not None else None,
-                          flt.clear_forcing if rhs is not None else None):
-                try:                                            # (a failure above is the one to report, not one of the clear)
-                    if clear is not None:
-                        clear()
-                except _hip.PnmolHipError:
-                    pass
+        slots = [flt.new_state() for _ in plan.dts]             # one per step: the recorder fills them
+        with self._loop_options(flt, plan, slots) as installed:
+            # (the loop advances its state in place: it works on a copy, the initial state stays what `ys[0]` holds)
+            work = state._replace(y=rv.DeviceMultivariateNormal(first.mean, first.device_state.clone()))
+            _, _, _, sig, _ = self._run_device_loop(pde, work, plan.ts, plan.dts)
+            lls = self._loop_consumed(flt, plan, installed, lls)
+            # one read-back for all states
+            means = flt.recorder_means(0, len(slots)) if slots else np.zeros((0,) + first.mean.shape)
         states = [first] + [rv.DeviceMultivariateNormal(m, s) for m, s in zip(means, slots)]
-        info = dict(num_steps=len(dts))
-        if obs is not None:
+        info = dict(num_steps=len(plan.dts))
+        if observations is not None:
             info.update(data_log_likelihood=float(sum(lls)), data_log_likelihoods=lls)
-        return pdefilter.PDESolution(t=np.array(ts), mean=np.stack([y.mean for y in states]), ys=states, info=info,
+        return pdefilter.PDESolution(t=np.array(plan.ts), mean=np.stack([y.mean for y in states]), ys=states, info=info,
                                      diffusion_squared_calibrated=np.mean(np.array(sig)))
 
     def smooth_marginals(self, solution):
@@ -617,13 +584,13 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         for smooth=None), `increments`, `num_iterations`, `converged`, and with observations `data_log_likelihood(s)` of the last
         pass.  One forward solution is alive at a time: memory is that of `solve_on_device`.  Supported: `SemiLinearWhiteNoiseEK1`
         in the fp64 covariance form with a term the device linearises, `Constant` steps."""
-        from . import latent, sqrtform
+        from . import latent
 
         if not isinstance(self.steprule, _step.Constant):
             raise TypeError("solve_iterated needs the Constant step rule")
         self._check_forcing_supported(pde)
-        if (not isinstance(self, SemiLinearWhiteNoiseEK1) or isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin))
-                or self.dtype != "f64" or self._reaction_for_device(pde) is None):
+        if (not isinstance(self, SemiLinearWhiteNoiseEK1) or isinstance(self, latent._LatentForceEK1Base)
+                or not self._is_fp64_covariance_form() or self._reaction_for_device(pde) is None):
             raise TypeError(f"solve_iterated() supports pnmol.white.SemiLinearWhiteNoiseEK1 in the fp64 covariance form on a problem "
                             f"whose term the device linearises (`pde.reaction`, reaction_on_device=True); "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} on this problem is not that")
@@ -658,9 +625,9 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
     def _walk_inputs(self, who, solution):
         """What `smooth`, `sample` and `sample_dense` walk backwards: (the device-resident states of `solution`, the one filter
         that owns them).  Refuses every solver but the fp64 covariance-form ones of pnmol.white."""
-        from . import latent, sqrtform
+        from . import latent
 
-        if isinstance(self, (latent._LatentForceEK1Base, sqrtform._SqrtFormMixin)) or self.dtype != "f64":
+        if isinstance(self, latent._LatentForceEK1Base) or not self._is_fp64_covariance_form():
             raise TypeError(f"{who}() supports the fp64 white-noise solvers of pnmol.white (covariance form); "
                             f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} is not one")
         ys = list(solution._ys)
@@ -862,11 +829,8 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
     reaction_on_device = True
 
     def _reaction_for_device(self, pde):
-        from . import sqrtform
-
         reaction = getattr(pde, "reaction", None)
-        if (reaction is None or not self.reaction_on_device or self.dtype != "f64"
-                or isinstance(self, sqrtform._SqrtFormMixin)):
+        if reaction is None or not self.reaction_on_device or not self._is_fp64_covariance_form():
             return None
         return reaction
 
