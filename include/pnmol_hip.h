@@ -32,7 +32,8 @@
  *     `_recorder_means`), the one-call backward pass (`pnmol_smoother_steps`) and the linearisation points of the loop
  *     (`pnmol_filter_set_linearization_points`, `_linearization_pending`, `pnmol_filter_linearize_at`) and the posterior of
  *     linear functionals of the trajectory (`pnmol_functionals`), and the forcing of driven problems
- *     (`pnmol_filter_set_forcing`, `_forcing_pending`, `pnmol_filter_force_at`).
+ *     (`pnmol_filter_set_forcing`, `_forcing_pending`, `pnmol_filter_force_at`), and time-dependent operators
+ *     (`pnmol_filter_set_operator_family`, `_set_operator_schedule`, `_operator_schedule_pending`, `pnmol_filter_operator_at`).
  *     Zero-initialise `pnmol_filter_desc`: unknown `dtype` values are rejected with -1.
  *   - dtype: fp64 (the reference runs with jax_enable_x64, src/pnmol/__init__.py:9-11); `pnmol_filter_desc.dtype = 1`
  *     keeps the covariance and its bulk kernels in fp32 (build-side option).
@@ -282,6 +283,51 @@ int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d);
 int pnmol_filter_set_forcing(pnmol_filter* f, int count, const double* rhs_cm);
 int pnmol_filter_forcing_pending(const pnmol_filter* f, int* next, int* count);
 int pnmol_filter_force_at(pnmol_filter* f, const double* rhs_m);
+
+/* Time-dependent operators: u_t = sum_r a_r(t) L_r u ----------------------------------------------------------------------------
+ * M(t) = sum_{r<R} a_r(t) L_r with R <= PNMOL_OPERATOR_MAXR fixed (d, d) stencil operators and scalar coefficients: a conductivity
+ * that changes in time, transport in an oscillating flow.  The step that lands on t measures with H = [E1 - M(t) E0; B E0] and the
+ * noise of its PDE rows is that of the operator, R_pde(t) = diag(sum_r (a_r(t) e_{r,i})^2), e_r the diagonal of the FD uncertainty
+ * E_sqrtm_r that came with L_r (errors of different operators are taken as independent; only diagonal E_sqrtm_r).  Boundary rows,
+ * their noise, the prior and the whole backward pass are untouched.  For fp64 white-noise filters (d_state = d) whose noise at
+ * creation is diagonal.
+ * `pnmol_filter_set_operator_family(f, R, L_Rdd, e_Rd)`: L_Rdd is (R, d, d) row-major, e_Rd (R, d).  Builds the union image of the
+ * L_r on top of the operator given at creation: every PDE row gets a slot for each column in which any L_r has an entry, in
+ * ascending column order, and one for the diagonal; boundary rows and padding are those of the creation-time image; the stencil
+ * grows if the union is wider.  The image does not depend on the coefficients (one may be zero at t0).  Until the first
+ * `pnmol_filter_operator_at` or loop step with a schedule the filter measures with the operator and the noise given at creation;
+ * the shift is zeroed.  Synchronises, drops the captured graphs, forgets the error model and the schedule of a family set before.
+ * R = 0 or a NULL argument clears: the creation-time image and noise come back, and the filter behaves bit for bit like one that
+ * never had a family.  -1 (reason in `pnmol_last_error`, nothing enqueued): null filter, R outside [1, 4], an entry of L or e that
+ * is not finite (operator, row and column are named), a latent-force or fp32 filter, noise at creation that is not diagonal, a
+ * filter whose operator or shift was replaced by `pnmol_filter_set_operator(_diagonal)` (image and clearing start from the
+ * creation-time operator and would lose it; setting a term, or clearing one, restores the creation-time operator and lifts the refusal), a
+ * reaction system or a convection term set (both bring a widened image of their own; `pnmol_filter_set_reaction_system` and
+ * `pnmol_filter_set_convection` refuse likewise while a family is set), called between `pnmol_filter_steps_begin` and `_end`.
+ * -4: out of memory.
+ * `pnmol_filter_set_operator_schedule(f, count, a_cR)`: a_cR is (count, R) row-major; row k is consumed by the k-th step
+ * `pnmol_filter_steps(_begin)` takes from now on, with the semantics of `pnmol_filter_set_forcing`: rows are consumed across calls
+ * (a runt last step takes its own row), a call that fails consumes none, `pnmol_filter_prepare_steps` consumes none, more steps
+ * asked for than rows left returns -1 from `pnmol_filter_steps(_begin)` with the state untouched, count = 0 or NULL clears.  A
+ * table that fits the one before it is overwritten in place and the captured graphs replay on it; the cursor goes to row 0.  The
+ * row is addressed on the device (a cursor word plus the loop's step counter).  While a schedule is set the loop takes the
+ * self-contained steps and carries no error model (H changes with every step); the order per step is operator, linearise, force,
+ * step, observation update, record.  Composes with a pointwise reaction (`pnmol_filter_set_reaction`: the diagonal of r' goes on
+ * top of M(t)), the table of linearisation points, forcing, the sensor plan and the recorder.  -1: null filter, no family set,
+ * latent-force or fp32 filter, count < 0, an entry that is not finite (row and column are named), called inside a call.
+ * `pnmol_filter_operator_schedule_pending`: the cursor and the number of rows (0, 0: no table).
+ * `pnmol_filter_operator_at(f, a_R)`: the single-step counterpart -- the same kernel on R numbers waiting in mapped host memory,
+ * enqueued at once, no synchronisation.  The operator and its noise PERSIST until another call or a loop step with a schedule
+ * replaces them.  The error model is forgotten: `pnmol_filter_prepare_error_model` comes next if one is wanted, then (with a
+ * reaction) `pnmol_filter_linearize`, then `pnmol_filter_step`.  -1: null filter or coefficients, no family, not finite, inside a
+ * call.
+ * While a family is set, `pnmol_filter_set_operator` and `pnmol_filter_set_operator_diagonal` return -1, as they do with a term or
+ * forcing. */
+#define PNMOL_OPERATOR_MAXR 4
+int pnmol_filter_set_operator_family(pnmol_filter* f, int R, const double* L_Rdd, const double* e_Rd);
+int pnmol_filter_set_operator_schedule(pnmol_filter* f, int count, const double* a_cR);
+int pnmol_filter_operator_schedule_pending(const pnmol_filter* f, int* next, int* count);
+int pnmol_filter_operator_at(pnmol_filter* f, const double* a_R);
 
 /* states ----------------------------------------------------------------------------- */
 int pnmol_state_create(pnmol_filter* f, pnmol_state** out);

@@ -3108,9 +3108,10 @@ enum StepKind { STEP_FULL = 0, STEP_FIRST = 1, STEP_STEADY = 2 };
 // steps write P only in the call's last step, while the update conditions P itself.  Nor while a recorder is set
 // (pnmol_filter_set_recorder): it copies the posterior P behind every step, which the fused steady-state launch never writes.
 // Nor while a table of right-hand sides is set (pnmol_filter_set_forcing): the next step's z needs that step's row in place.
+// Nor while a schedule of operator coefficients is set (pnmol_filter_set_operator_schedule): the next step's H changes first.
 inline bool fused_loop(const pnmol_filter* f) {
     return f->sweep_mode == 2 && f->n <= 3 && f->fuse_predict != 0 && !has_term(f) && !pnmol_observe_plan_pending(f) &&
-           !pnmol_record_active(f) && !pnmol_forcing_table_set(f);
+           !pnmol_record_active(f) && !pnmol_forcing_table_set(f) && !pnmol_operator_schedule_set(f);
 }
 
 // the sweep launch: right-looking register-resident kernel where the row block fits the registers (CB <= 17: N <= 512 in 1-d),
@@ -3285,6 +3286,8 @@ int dispatch_step(pnmol_filter* f, const double* Pin, const double* min, double 
 // at once and the caller records behind it)
 int loop_step(pnmol_filter* f, const double* Pin, const double* min, double frame_dt, double dt, double* Pout, double* mout,
               double* varout, StepKind kind, bool keep = true) {
+    // a schedule of operator coefficients: this step's row makes the operator and its noise first (k_operator_at, pnmol_operator.hip)
+    if (int rc = pnmol_operator_enqueue_loop(f)) return rc;
     if (has_term(f)) {
         if (int rc = pnmol_reaction_enqueue(f, min, frame_dt, dt, true)) return rc;
     }
@@ -3486,6 +3489,7 @@ int pnmol_ell_restore_base(pnmol_filter* f, bool for_term) {
         HIPCHK(ctx, hipMemcpyAsync(f->ell_col, f->ell_col_base, sizeof(int) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(f->ell_val, f->ell_val_base, sizeof(double) * (size_t)f->base_w * mp, hipMemcpyDeviceToDevice, st));
     if (for_term) HIPCHK(ctx, hipMemsetAsync(f->shift, 0, sizeof(double) * mp, st));
+    if (for_term) f->op_replaced = 0;  // (values and shift are those of creation again)
     f->ellw = f->base_w;
     f->ell_is_base = 1;
     return 0;
@@ -3885,6 +3889,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_record_free(f);
     pnmol_reaction_free_ws(f);
     pnmol_forcing_free(f);
+    pnmol_operator_free(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -3975,6 +3980,10 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
         ctx->err = "pnmol_filter_set_operator: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
         return -1;
     }
+    if (pnmol_operator_family_set(f)) {
+        ctx->err = "pnmol_filter_set_operator: clear the operator family first (pnmol_filter_set_operator_family(f, 0, NULL, NULL))";
+        return -1;
+    }
     if (pnmol_forcing_set(f)) {
         ctx->err = "pnmol_filter_set_operator: clear the forcing first (pnmol_filter_set_forcing(f, 0, NULL), pnmol_filter_force_at(f, NULL))";
         return -1;
@@ -3988,6 +3997,7 @@ int pnmol_filter_set_operator(pnmol_filter* f, const double* M_dd, const double*
     if (int rc = pnmol_ell_reserve(f, w)) return rc;
     f->ellw = w;
     f->ell_is_base = 0;
+    f->op_replaced = 1;  // (a family starts from the operator given at creation: pnmol_filter_set_operator_family refuses from here on)
     HIPCHK(ctx, hipMemcpy(f->ell_col, ecol.data(), sizeof(int) * ecol.size(), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(f->ell_val, eval.data(), sizeof(double) * eval.size(), hipMemcpyHostToDevice));
     std::vector<double> sh((size_t)f->mp, 0.0);
@@ -4001,6 +4011,10 @@ int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, c
     pnmol_ctx* ctx = f->ctx;
     if (has_term(f)) {
         ctx->err = "pnmol_filter_set_operator_diagonal: clear the reaction first (pnmol_filter_set_reaction(f, NULL))";
+        return -1;
+    }
+    if (pnmol_operator_family_set(f)) {
+        ctx->err = "pnmol_filter_set_operator_diagonal: clear the operator family first (pnmol_filter_set_operator_family(f, 0, NULL, NULL))";
         return -1;
     }
     if (pnmol_forcing_set(f)) {
@@ -4018,6 +4032,7 @@ int pnmol_filter_set_operator_diagonal(pnmol_filter* f, const double* jdiag_d, c
     const int d = f->d, mp = f->mp;
     std::memcpy(f->h_op, jdiag_d, sizeof(double) * d);
     for (int i = 0; i < mp; ++i) f->h_op[d + i] = (shift_d && i < d) ? shift_d[i] : 0.0;
+    f->op_replaced = 1;
     // after a dense pnmol_filter_set_operator: back to the base image, whatever its width (a dense M of L's width can hold other
     // off-diagonal values, or -- build_ell drops exact zeros -- another row pattern that moves the diagonal out of ell_diag_slot).
     // The copies go into the same buffers: captured graphs stay valid unless the width changes.
@@ -4106,6 +4121,9 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     // a table of right-hand sides: the same
     rc = pnmol_forcing_begin(f, k);
     if (rc != 0) return rc;
+    // a schedule of operator coefficients: the same
+    rc = pnmol_operator_begin(f, k);
+    if (rc != 0) return rc;
     // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
     std::vector<int> ob_entry;
     rc = pnmol_observe_plan_begin(f, s, k, dt, &ob_entry);
@@ -4123,6 +4141,8 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     if ((rc = pnmol_record_enqueue_cursor(f)) != 0) return rc;
     if ((rc = pnmol_linearize_enqueue_cursor(f)) != 0) return rc;
     if ((rc = pnmol_forcing_enqueue_cursor(f)) != 0) return rc;
+    if ((rc = pnmol_operator_enqueue_cursor(f)) != 0) return rc;
+    if (pnmol_operator_schedule_set(f)) f->sq_dt = -1.0;  // H changes with every step: no error model either
     if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
     double *curP = s->P, *curM = s->mean, *nxtP = f->tmpP, *nxtM = f->tmpMean;
@@ -4242,6 +4262,7 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
     // a table of linearisation points: the call's rows are consumed, unless it failed (the cursor then stays where the call began)
     pnmol_linearize_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);
     pnmol_forcing_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);  // (a table of right-hand sides: the same rule)
+    pnmol_operator_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);  // (a schedule of operator coefficients: the same)
     if (ob_rc != 0) {
         const int first = stuck >= 0 && (bad < 0 || stuck < bad) ? stuck : bad;  // the first step that failed by itself
         if (first < 0 || first > ob_step) return ob_rc;                         // (ctx->err names entry, pivot and step)
@@ -4285,11 +4306,13 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
         const int rec_next = pnmol_record_cursor(f);       // (a recorder: the rehearsal fills slots the real call fills again)
         const int lin_next = pnmol_linearize_cursor(f);    // (linearisation points: the rehearsal consumes rows of the real call)
         const int frc_next = pnmol_forcing_cursor(f);      // (right-hand sides: the same)
+        const int opr_next = pnmol_operator_cursor(f);     // (operator coefficients: the same)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
         pnmol_observe_plan_rewind(f, ob_next);
         pnmol_record_rewind(f, rec_next);
         pnmol_linearize_rewind(f, lin_next);
         pnmol_forcing_rewind(f, frc_next);
+        pnmol_operator_rewind(f, opr_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

@@ -125,6 +125,7 @@ struct pnmol_filter {
     double* ell_val_base = nullptr;
     int* ell_diag_slot = nullptr;
     int base_w = 0, base_has_diag = 0;
+    int op_replaced = 0;      // pnmol_filter_set_operator / _set_operator_diagonal have replaced the creation-time operator or shift
     int ell_is_base = 1;      // ell_col / ell_val hold the base image (diagonal slots aside): no dense upload since the last restore
     double* h_op = nullptr;
     double* h_op_dev = nullptr;
@@ -216,6 +217,11 @@ struct pnmol_filter {
     // constant-step loop runs non-fused and its i-th step taken since measures against row i; a forced step reads its shift from a
     // buffer of the forcing's own, so `shift` stays what the operator setters and the term kernels made it.
     struct ForcingDev* forcing = nullptr;
+    // A time-dependent operator M(t) = sum_r a_r(t) L_r (pnmol_filter_set_operator_family, pnmol_operator.hip): NULL = none.  While
+    // a family is set ell_col / ell_val hold its union image, the operator setters and the terms with an image of their own refuse,
+    // and a pointwise reaction linearises on the family's current operator.  While a schedule of coefficients is set as well the
+    // constant-step loop runs non-fused, without an error model, and its i-th step taken since runs with row i.
+    struct OperatorDev* op_family = nullptr;
     // Linear functionals of the trajectory (pnmol_functionals, pnmol_functional.hip): the workspace of the pass, allocated on first use
     struct FunctionalWs* fn_ws = nullptr;
 };
@@ -366,6 +372,26 @@ void pnmol_forcing_collect(pnmol_filter* f, int k, bool ok);
 int pnmol_forcing_cursor(const pnmol_filter* f);
 void pnmol_forcing_rewind(pnmol_filter* f, int next);
 void pnmol_forcing_free(pnmol_filter* f);
+// pnmol_operator.hip: the time-dependent operator.  family_set: the operator setters and the wide terms refuse; schedule_set: a table
+// of coefficients is set (the loop then runs non-fused: the next step's H is not in place before its row has been applied).
+bool pnmol_operator_family_set(const pnmol_filter* f);
+bool pnmol_operator_schedule_set(const pnmol_filter* f);
+// with a family set: the values and the diagonal-slot table a pointwise reaction linearises on (the current operator and the union
+// image's slots) in place of the creation-time ones; without: both pointers stay what they are
+void pnmol_operator_linearize_base(const pnmol_filter* f, const double** base_val, const int** slot);
+// the family's image with the current operator into ell_col / ell_val (grown if it is wider), and a zero shift: what
+// pnmol_ell_restore_base is to a filter without a family.  Needs a family; the caller has dropped the graphs.
+int pnmol_operator_put_image(pnmol_filter* f);
+// k_operator_at in front of a step of the loop (the row the device words name), on the ctx stream, in front of the step's linearise
+// launch.  Without a schedule nothing is enqueued.  -2: the launch failed.
+int pnmol_operator_enqueue_loop(pnmol_filter* f);
+// the table inside a call, as the table of right-hand sides above: refusal of k steps, cursor words, collect, cursor and rewind
+int pnmol_operator_begin(pnmol_filter* f, int k);
+int pnmol_operator_enqueue_cursor(pnmol_filter* f);
+void pnmol_operator_collect(pnmol_filter* f, int k, bool ok);
+int pnmol_operator_cursor(const pnmol_filter* f);
+void pnmol_operator_rewind(pnmol_filter* f, int next);
+void pnmol_operator_free(pnmol_filter* f);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);
 // pnmol_hip.hip: make ell_col / ell_val at least w slots wide.  Growing frees them (ellw = 0 until the caller has filled them): the

@@ -349,6 +349,10 @@ std::string capability_fault(const pnmol_filter* f, const char* path) {
     return {};
 }
 
+// a reaction system and a convection term widen the image themselves, and so does a time-dependent operator: one at a time
+const char* const FAMILY_HOLDS_THE_IMAGE =
+    "a time-dependent operator is set (pnmol_filter_set_operator_family): clear it first, both bring a widened image of their own";
+
 int refuse(pnmol_filter* f, const char* who, const std::string& why) {
     f->ctx->err = std::string(who) + why;
     return -1;
@@ -442,13 +446,16 @@ int install_term(pnmol_filter* f, TermKind kind, int ncomp = 0, const double* G 
         free_linearize_table(f);
     }
     const bool image = kind == TermKind::system || kind == TermKind::convection;
-    const int rc = image ? put_term_image(f, kind, ncomp, G) : pnmol_ell_restore_base(f, true);
+    // (a time-dependent operator, pnmol_operator.hip: its image with the current operator is what a pointwise reaction patches)
+    const int rc = image ? put_term_image(f, kind, ncomp, G)
+                         : (pnmol_operator_family_set(f) ? pnmol_operator_put_image(f) : pnmol_ell_restore_base(f, true));
     f->sq_dt = -1.0;  // the error model belongs to the operator that was set
     f->term = rc ? TermKind::none : kind;
     if (rc) {
         const std::string err = f->ctx->err;
         free_term_image(f);
-        (void)pnmol_ell_restore_base(f, true);
+        if (pnmol_operator_family_set(f)) (void)pnmol_operator_put_image(f);
+        else (void)pnmol_ell_restore_base(f, true);
         f->ctx->err = err;
     }
     return rc;
@@ -469,10 +476,15 @@ int enqueue_linearize(pnmol_filter* f, const double* mean, double frame_dt, doub
     const TermImage& im = f->term_img;
     switch (f->term) {
         case TermKind::none: return -1;
-        case TermKind::scalar:
-            k_linearize<<<blocks, 256, 0, st>>>({f->reaction, fr, pt}, f->n, mean, f->ell_val, f->ell_val_base, f->ell_diag_slot,
-                                                f->shift, f->d, f->dp, f->mp);
+        case TermKind::scalar: {
+            // (a time-dependent operator: the current operator and the union image's diagonal slots in place of the base ones)
+            const double* base_val = f->ell_val_base;
+            const int* slot = f->ell_diag_slot;
+            pnmol_operator_linearize_base(f, &base_val, &slot);
+            k_linearize<<<blocks, 256, 0, st>>>({f->reaction, fr, pt}, f->n, mean, f->ell_val, base_val, slot, f->shift, f->d, f->dp,
+                                                f->mp);
             break;
+        }
         case TermKind::system:
             k_linearize_system<<<blocks, 256, 0, st>>>({f->sys, fr, pt}, f->n, f->d / f->sys.ncomp, mean, f->ell_val, im.val, im.slot,
                                                        f->shift, f->d, f->dp, f->mp);
@@ -625,6 +637,7 @@ int pnmol_filter_set_reaction_system(pnmol_filter* f, const pnmol_reaction_syste
     pnmol_ctx* ctx = f->ctx;
     const char* fault = system_descriptor_fault(r);
     if (!fault && f->d % r->ncomp != 0) fault = "d is not a multiple of ncomp";
+    if (!fault && pnmol_operator_family_set(f)) fault = FAMILY_HOLDS_THE_IMAGE;
     const std::string why = fault ? fault : capability_fault(f, "pointwise reaction path");
     if (!why.empty()) return refuse(f, who, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -651,6 +664,7 @@ int pnmol_filter_set_convection(pnmol_filter* f, const pnmol_convection* term, c
     if (!fault && (term->deg_c < -1 || term->deg_c > PNMOL_REACTION_MAXDEG)) fault = "a degree outside [-1, 7]";
     if (!fault) fault = reaction_descriptor_fault(&term->r);
     if (!fault && !all_finite(term->c, term->deg_c)) fault = "a coefficient is not finite";
+    if (!fault && pnmol_operator_family_set(f)) fault = FAMILY_HOLDS_THE_IMAGE;
     std::string why = fault ? fault : capability_fault(f, "convection path");
     if (why.empty())
         for (size_t k = 0; k < (size_t)f->d * f->d && why.empty(); ++k)

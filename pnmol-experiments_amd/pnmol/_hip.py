@@ -84,6 +84,10 @@ SYMBOLS = {
     "pnmol_filter_set_forcing": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p]),
     "pnmol_filter_forcing_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pnmol_filter_force_at": (ctypes.c_int, [_vp, _c_double_p]),
+    "pnmol_filter_set_operator_family": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p, _c_double_p]),
+    "pnmol_filter_set_operator_schedule": (ctypes.c_int, [_vp, ctypes.c_int, _c_double_p]),
+    "pnmol_filter_operator_schedule_pending": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pnmol_filter_operator_at": (ctypes.c_int, [_vp, _c_double_p]),
     "pnmol_state_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pnmol_state_destroy": (ctypes.c_int, [_vp]),
     "pnmol_state_clone": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
@@ -327,6 +331,8 @@ class Filter:
         self.d, self.n, self.nB, self.m = d, int(num_derivatives) + 1, nB, d + nB
         self.error_model_dt = None
         self.reaction = None        # the pde.reactions.Reaction the device evaluates (`set_reaction`)
+        self.operator_family = 0    # number of operators of the family set (`set_operator_family`), 0: none
+        self._operator_schedule = False
         # raw handles of the live pnmol_state objects of this filter, keyed by id(State): the C ABI refuses to destroy a
         # filter that still has states (include/pnmol_hip.h, "Lifetimes").  A plain dict, not weak references: the
         # cyclic collector clears weakrefs to unreachable objects BEFORE it runs finalisers, so a WeakSet would be empty
@@ -489,6 +495,59 @@ class Filter:
         synchronisation); None returns the filter to unforced."""
         r = None if rhs is None else _f64(rhs, (self.m,))
         self.ctx.check(self.lib.pnmol_filter_force_at(self.handle, None if r is None else _dp(r)), "pnmol_filter_force_at")
+
+    def set_operator_family(self, operators, noise_diagonals):
+        """A time-dependent operator M(t) = sum_r a_r(t) L_r (`pnmol_filter_set_operator_family`): `operators` (R, d, d) and the
+        diagonals (R, d) of their FD uncertainties, R <= 4.  Until `operator_at` or a loop step with a schedule the filter
+        measures with the operator given at creation."""
+        L = _f64(operators)
+        e = _f64(noise_diagonals)
+        if L.ndim != 3 or L.shape[0] < 1 or L.shape[1:] != (self.d, self.d) or e.shape != (L.shape[0], self.d):
+            raise ValueError(f"operators must be (R, {self.d}, {self.d}) and noise_diagonals (R, {self.d}) with R >= 1, got "
+                             f"{L.shape} and {e.shape} (clear_operator_family() drops the family)")
+        self.ctx.check(self.lib.pnmol_filter_set_operator_family(self.handle, L.shape[0], _dp(L), _dp(e)),
+                       "pnmol_filter_set_operator_family")
+        self.operator_family = L.shape[0]
+        self._operator_schedule = False
+        self.error_model_dt = None
+
+    def clear_operator_family(self):
+        """Drop the family and its schedule: the filter then gives the bits of one that never had a family."""
+        self.ctx.check(self.lib.pnmol_filter_set_operator_family(self.handle, 0, None, None), "pnmol_filter_set_operator_family")
+        self.operator_family = 0
+        self._operator_schedule = False
+        self.error_model_dt = None
+
+    def set_operator_schedule(self, coefficients):
+        """Coefficients for the constant-step loop (`pnmol_filter_set_operator_schedule`): (count, R); the k-th step `steps` takes
+        from now on runs with M = sum_r coefficients[k, r] L_r and its noise.  The cursor starts at row 0."""
+        a = _f64(coefficients)
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != max(self.operator_family, 1):
+            raise ValueError(f"coefficients must be (count, {max(self.operator_family, 1)}) with count >= 1, got {a.shape} "
+                             "(clear_operator_schedule() drops the table)")
+        self.ctx.check(self.lib.pnmol_filter_set_operator_schedule(self.handle, a.shape[0], _dp(a)),
+                       "pnmol_filter_set_operator_schedule")
+        self._operator_schedule = True
+
+    def clear_operator_schedule(self):
+        """Drop the table: the operator stays what the last step made it."""
+        self.ctx.check(self.lib.pnmol_filter_set_operator_schedule(self.handle, 0, None), "pnmol_filter_set_operator_schedule")
+        self._operator_schedule = False
+
+    def operator_schedule_pending(self):
+        """(next, count): the table's cursor -- the row the next step runs with -- and its number of rows ((0, 0): none)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.pnmol_filter_operator_schedule_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
+                       "pnmol_filter_operator_schedule_pending")
+        return nxt.value, n.value
+
+    def operator_at(self, coefficients):
+        """The operator and its noise from the R coefficients (`pnmol_filter_operator_at`; enqueued at once, no synchronisation),
+        until another call or a loop step with a schedule replaces them.  Then `linearize` (with a reaction), then
+        `prepare_error_model(dt)` if the error estimate is wanted, then `step`."""
+        a = _f64(coefficients, (max(self.operator_family, 1),))
+        self.ctx.check(self.lib.pnmol_filter_operator_at(self.handle, _dp(a)), "pnmol_filter_operator_at")
+        self.error_model_dt = None
 
     def step(self, state_in, dt, want_error=True):
         out = State(self)
@@ -672,14 +731,14 @@ class Filter:
         rc = self.lib.pnmol_filter_steps(self.handle, state.handle, int(k), float(dt),
                                          _dp(means) if want_means else None, _dp(stds) if want_stds else None, infos)
         self.ctx.check(rc, "pnmol_filter_steps")
-        if self.reaction is not None:
+        if self.reaction is not None or self._operator_schedule:
             self.error_model_dt = None      # (the loop re-linearises: an error model prepared before is forgotten)
         return means, stds, infos
 
     def steps_begin(self, state, k, dt):
         self.ctx.check(self.lib.pnmol_filter_steps_begin(self.handle, state.handle, int(k), float(dt)),
                        "pnmol_filter_steps_begin")
-        if self.reaction is not None:
+        if self.reaction is not None or self._operator_schedule:
             self.error_model_dt = None      # (the loop re-linearises: an error model prepared before is forgotten)
         self._pending_k = int(k)
 

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 
 from .. import diffops, discretize, kernels, mesh
+from . import coefficients as _coefficients
 from . import forcing as _forcing
 from . import problems, reactions
 
@@ -236,6 +237,52 @@ def convection_diffusion_1d_discretized(term, *, bbox=None, t0=0.0, tmax=10.0, d
                                        stencil_size_boundary=gradient_stencil_size, nugget_gram_matrix=nugget_gram_matrix_fd)
     term.set_operator(G)
     return _forcing.attach(pde, forcing, f)
+
+
+def _time_varying_base(reaction, forcing, **kw):
+    """The problem the two recipes below start from, discretised with a unit diffusion rate: (pde, Laplacian, its E_sqrtm)."""
+    if reaction is None:
+        pde = heat_1d_discretized(diffusion_rate=1.0, forcing=forcing, **kw)
+    else:
+        y0_fun = heat_1d(bbox=kw["bbox"], bcond=kw["bcond"]).y0_fun        # (the initial values of the heat recipe, reaction or not)
+        pde = reaction_diffusion_1d_discretized(reaction, diffusion_rate=1.0, forcing=forcing, y0_fun=y0_fun, **kw)
+    return pde, pde.L, pde.E_sqrtm
+
+
+def heat_1d_time_varying_discretized(*, diffusion_rate, reaction=None, forcing=None, bbox=None, dx=0.05, t0=0.0, tmax=5.0,
+                                     stencil_size_interior=3, stencil_size_boundary=3, nugget_gram_matrix_fd=0.0, kernel=None,
+                                     bcond="dirichlet"):
+    """u_t = kappa(t) u_xx [+ r(u)] [+ s(t, x)]: `diffusion_rate` is a callable t -> kappa(t).  The problem carries
+    `pde.time_dependent_operator` (pde/coefficients.py) with the one operator u_xx and its FD uncertainty; `pde.L` and
+    `pde.E_sqrtm` are those of t0.  reaction: a scalar `pnmol.pde.reactions.Reaction` or None; forcing: as in
+    `heat_1d_discretized`."""
+    if not callable(diffusion_rate):
+        raise TypeError("heat_1d_time_varying_discretized: diffusion_rate must be a callable t -> kappa(t)")
+    pde, lap, lap_e = _time_varying_base(reaction, forcing, bbox=bbox, dx=dx, t0=t0, tmax=tmax, bcond=bcond, kernel=kernel,
+                                         stencil_size_interior=stencil_size_interior, stencil_size_boundary=stencil_size_boundary,
+                                         nugget_gram_matrix_fd=nugget_gram_matrix_fd)
+    return _coefficients.attach(pde, _coefficients.TimeDependentOperator([lap], [lap_e], diffusion_rate))
+
+
+def advection_diffusion_1d_discretized(diffusion_rate, *, velocity, reaction=None, forcing=None, bbox=None, dx=0.05, t0=0.0,
+                                       tmax=5.0, stencil_size_interior=3, stencil_size_boundary=3, gradient_stencil_size=3,
+                                       nugget_gram_matrix_fd=0.0, kernel=None, bcond="dirichlet"):
+    """u_t = kappa u_xx - c(t) u_x [+ r(u)] [+ s(t, x)]: transport in a flow whose `velocity` is a callable t -> c(t).  The gradient
+    is the kernel finite-difference one on its own neighbour sets (`gradient_stencil_size` points), and -- unlike the convection
+    recipe above -- its FD uncertainty is part of the model: the noise of the PDE rows is diag((kappa e_lap)^2 + (c(t) e_grad)^2).
+    `pde.time_dependent_operator` holds (u_xx, u_x) with the coefficients (kappa, -c(t))."""
+    if not callable(velocity):
+        raise TypeError("advection_diffusion_1d_discretized: velocity must be a callable t -> c(t)")
+    kappa = float(diffusion_rate)
+    pde, lap, lap_e = _time_varying_base(reaction, forcing, bbox=bbox, dx=dx, t0=t0, tmax=tmax, bcond=bcond, kernel=kernel,
+                                         stencil_size_interior=stencil_size_interior, stencil_size_boundary=stencil_size_boundary,
+                                         nugget_gram_matrix_fd=nugget_gram_matrix_fd)
+    grad, grad_e = discretize.fd_probabilistic(diffops.gradient(), mesh_spatial=pde.mesh_spatial,
+                                               kernel=kernel or kernels.SquareExponential(),
+                                               stencil_size_interior=gradient_stencil_size,
+                                               stencil_size_boundary=gradient_stencil_size, nugget_gram_matrix=nugget_gram_matrix_fd)
+    operator = _coefficients.TimeDependentOperator([lap, grad], [lap_e, grad_e], lambda t: (kappa, -float(velocity(t))))
+    return _coefficients.attach(pde, operator)
 
 
 def burgers_1d_discretized(viscosity=0.02, **kwargs):

@@ -32,9 +32,10 @@ IteratedSolution.__doc__ = """Result of `solve_iterated`: the last pass's filter
 the `smooth()` solution of the last pass (or None), the relative increment of every pass beyond pass 0, their number, whether the
 last increment met the tolerance, and with observations the data log-likelihoods of the last pass (else None)."""
 
-_LoopPlan = collections.namedtuple("_LoopPlan", "ts dts points forcing observations sensors at_t0")
+_LoopPlan = collections.namedtuple("_LoopPlan", "ts dts points forcing operator observations sensors at_t0")
 _LoopPlan.__doc__ = """What one run of the device-resident constant-step loop needs, validated on the host (`_loop_plan`): the schedule
-`ts` / `dts`; per option its table or None -- `points` (T, d) to linearise at, `forcing` (T, m) right-hand sides --; `observations` as
+`ts` / `dts`; per option its table or None -- `points` (T, d) to linearise at, `forcing` (T, m) right-hand sides, `operator` (T, R)
+coefficients of a time-dependent operator --; `observations` as
 `data.prepare` returns them (None: the caller gave none); `sensors` = (times, C, R_sqrtm, ys) of the shared sensor array for the
 observations behind t0 (None: there are none); `at_t0`: whether `observations[0]` sits at t0 and updates the initial state."""
 
@@ -101,6 +102,9 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         self._device_pde = pde
         self._gram = gram
         self._error_models = {}
+        operator = getattr(pde, "time_dependent_operator", None)
+        if operator is not None:                                # (checked by `_check_operator_supported` in front of `_bind`)
+            self._device_filter.set_operator_family(operator.operators, operator.noise_diagonals)
         if self._reaction_for_device(pde) is not None:
             self._device_filter.set_reaction(pde.reaction)
 
@@ -108,10 +112,32 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         """The reaction term the device evaluates itself for this solver and problem, or None (host callables)."""
         return None
 
+    # ------------------------------------------------------------------ time-dependent operators
+    def _check_operator_supported(self, pde):
+        """A problem with `pde.time_dependent_operator` (pde/coefficients.py) is honoured or refused, never ignored: the refusal,
+        before any device work.  Returns the operator, or None."""
+        operator = getattr(pde, "time_dependent_operator", None)
+        if operator is None:
+            return None
+        from . import latent
+        from .pde.reactions import Reaction
+
+        is_latent = isinstance(self, latent._LatentForceEK1Base)
+        ok = (self._is_fp64_covariance_form() and not is_latent
+              and (not self.semilinear or isinstance(self._reaction_for_device(pde), Reaction)))
+        if not ok:
+            raise TypeError(f"pde.time_dependent_operator is honoured by the fp64 covariance-form solvers LinearWhiteNoiseEK1 and "
+                            f"SemiLinearWhiteNoiseEK1 with a scalar reaction the device linearises (`pde.reaction`, "
+                            f"reaction_on_device=True); "
+                            f"{type(self).__module__}.{type(self).__name__} with dtype={self.dtype!r} on this problem is not one")
+        return operator
+
     # ------------------------------------------------------------------ driven problems
     def _check_forcing_supported(self, pde):
         """A problem with `pde.forcing` (pde/forcing.py) is honoured or refused, never ignored: the refusal, before any device
-        work.  Returns the forcing, or None."""
+        work.  Returns the forcing, or None.  Every entry point of every solver class comes through here, so the refusal of a
+        time-dependent operator (`_check_operator_supported`) is made here as well."""
+        self._check_operator_supported(pde)
         forcing = getattr(pde, "forcing", None)
         if forcing is None:
             return None
@@ -274,7 +300,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
     def _ensure_error_model(self, pde, dt):
         if self._device_filter.error_model_dt != float(dt):
-            if self.error_model_on_host:
+            # (a time-dependent operator: the host form knows pde.L and pde.E_sqrtm, which are those of t0)
+            if self.error_model_on_host and getattr(pde, "time_dependent_operator", None) is None:
                 self._device_filter.set_error_model(dt, *self._error_model(pde, dt))
             else:
                 self._device_filter.prepare_error_model(dt)   # Sq factorised by the step's own kernels
@@ -299,7 +326,13 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
     def attempt_step(self, state, dt, pde):
         """One predict + update + calibrate step on the GPU (white.py:96-146); `state` is not modified."""
+        self._check_operator_supported(pde)
         dev_in = self._device_state_of(state, pde)
+        operator = getattr(pde, "time_dependent_operator", None)
+        if operator is not None:
+            # in front of linearise / force: M(t + dt) and its noise from R numbers (`pnmol_filter_operator_at`); the error model
+            # is forgotten, so the branches below prepare it for this operator
+            self._device_filter.operator_at(operator.coefficients(state.t + dt))
         if self.semilinear and self._device_filter.reaction is not None:
             # pointwise reaction described to the device (pde/reactions.py): linearised there at the predicted mean, nothing
             # comes back and nothing goes up
@@ -380,6 +413,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
         ts, dts = self._constant_schedule(pde, num_steps)
         points = self._checked_linearization_points(pde, linearize_at, len(dts))
         forcing = self._forcing_table(pde, ts)
+        operator = self._operator_table(pde, ts)
         sensors, at_t0 = None, False
         if obs:
             dt0 = self.steprule.first_dt(pde)
@@ -389,7 +423,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             at_t0 = bool(data.times_agree(obs[0].t, pde.t0, dt0))   # that one updates the initial state, as solve() does it
             if times.size > at_t0:
                 sensors = (times[at_t0:], C, R, ys[at_t0:])
-        return _LoopPlan(ts, dts, points, forcing, obs, sensors, at_t0)
+        return _LoopPlan(ts, dts, points, forcing, operator, obs, sensors, at_t0)
 
     def _observe_at_t0(self, state, plan):
         """(`state` conditioned on the observation at t0, [its log-likelihood]); (`state`, []) where the plan has none there."""
@@ -416,6 +450,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
                 options["points"] = (lambda: flt.set_linearization_points(plan.points), flt.clear_linearization_points)
             if plan.forcing is not None:
                 options["forcing"] = (lambda: flt.set_forcing(plan.forcing), flt.clear_forcing)
+            if plan.operator is not None:
+                options["operator"] = (lambda: flt.set_operator_schedule(plan.operator), flt.clear_operator_schedule)
         attempted, failed = [], True
         try:
             for name, (install, _) in options.items():
@@ -425,7 +461,7 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             failed = False
         finally:
             errors = []
-            for name in ("recorder", "observations", "points", "forcing"):
+            for name in ("recorder", "observations", "points", "forcing", "operator"):
                 try:
                     if name in attempted:
                         options[name][1]()
@@ -451,6 +487,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             raise RuntimeError("the loop did not consume every linearisation point")
         if "forcing" in installed and flt.forcing_pending() != (T, T):
             raise RuntimeError("the loop did not consume every right-hand side of the forcing")
+        if "operator" in installed and flt.operator_schedule_pending() != (T, T):
+            raise RuntimeError("the loop did not consume every row of coefficients of the time-dependent operator")
         return lls
 
     def solve_marginals(self, pde, *, num_steps=None, observations=None, linearize_at=None):
@@ -492,6 +530,14 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
             return None
         return np.ascontiguousarray(forcing.table(ts, pde))
 
+    def _operator_table(self, pde, ts):
+        """The coefficients of `pde.time_dependent_operator` on the constant schedule `ts` (a runt last step included) as the (T, R)
+        table the device takes, or None: no such operator, or no step.  Validated on the host, in front of any device work."""
+        operator = self._check_operator_supported(pde)
+        if operator is None or len(ts) < 2:
+            return None
+        return np.ascontiguousarray(operator.table(ts))
+
     def _constant_schedule(self, pde, num_steps):
         """(times, steps) of the constant-step loop: the t-accumulation of the reference, a runt final step included."""
         return data.constant_schedule(pde.t0, pde.tmax, self.steprule.first_dt(pde), num_steps)
@@ -499,7 +545,8 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
     def _run_device_loop(self, pde, state, ts, dts):
         """The steps `dts` from `state` on the device, runs of equal dt in one call each: the 5-tuple of `solve_marginals`."""
         dev = state.y.device_state
-        on_device = self._device_filter.reaction is not None    # re-linearised inside the loop; no error model there
+        # re-linearised, or its operator rebuilt, inside the loop: no error model there
+        on_device = self._device_filter.reaction is not None or getattr(pde, "time_dependent_operator", None) is not None
         d = pde.L.shape[0]                                      # (the latent-force state carries eps behind u)
         means = [state.y.mean[0][:d]]
         stds = [np.sqrt(np.maximum(state.y.marginal_var[0][:d], 0.0))]
@@ -783,11 +830,13 @@ class _WhiteNoiseEK1Base(pdefilter.PDEFilter):
 
 
 class LinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
-    """EK1 for linear PDEs u_t = L u (white.py:169-186): H = [E1 - L E0 ; B E0], no shift."""
+    """EK1 for linear PDEs u_t = L u (white.py:169-186): H = [E1 - L E0 ; B E0], no shift.  A problem with
+    `pde.time_dependent_operator` (pde/coefficients.py): L is M(t)."""
 
     @staticmethod
     def _linearize(pde, m_at, t):
-        return pde.L, np.zeros(pde.L.shape[0])
+        operator = getattr(pde, "time_dependent_operator", None)
+        return (pde.L if operator is None else operator.matrix(t)), np.zeros(pde.L.shape[0])
 
 
 class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
@@ -811,7 +860,8 @@ class SemiLinearWhiteNoiseEK1(_WhiteNoiseEK1Base):
             return M, shift
         fx = np.asarray(pde.f(t, m_at), dtype=np.float64)
         Jx = np.asarray(pde.df(t, m_at), dtype=np.float64)
-        return pde.L + Jx, Jx @ m_at - fx
+        operator = getattr(pde, "time_dependent_operator", None)
+        return (pde.L if operator is None else operator.matrix(t)) + Jx, Jx @ m_at - fx
 
     @staticmethod
     def _jacobian_diagonal(pde, m_at, t):
