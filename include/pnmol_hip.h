@@ -258,7 +258,8 @@ int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d);
  * `pnmol_filter_set_forcing(f, count, rhs_cm)`: rhs_cm is (count, m) row-major; row k is consumed by the k-th step
  * `pnmol_filter_steps(_begin)` takes from now on.  Rows are consumed across calls (a schedule's runt last step takes its own row);
  * a call that fails (-2 / -3) consumes none, `pnmol_filter_prepare_steps` consumes none.  The table is copied to the device (row
- * stride mp, padding zero), the cursor goes to row 0; the call synchronises and drops the captured graphs.  The row is addressed on
+ * stride mp, padding zero), the cursor goes to row 0; the call synchronises.  A table that fits the one before it is overwritten in
+ * place and the captured graphs replay on it; any other change of the table drops them.  The row is addressed on
  * the device (a cursor word written once per call plus the loop's step counter), so every step launches with identical arguments and
  * the loop's graphs serve any position.  While a table is set the loop takes the self-contained steps (as with a term or a sensor
  * plan: the next innovation cannot be prepared before its right-hand side is in place).  Without a term H does not change, and the

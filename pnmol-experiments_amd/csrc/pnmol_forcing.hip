@@ -19,12 +19,8 @@
 #include "pnmol_forcing_plan.hpp"
 #include "pnmol_internal.hpp"
 
-// host logic in pnmol_forcing_plan.hpp; rows and words live on the device
+// what a forced step needs beside the loop's table (pnmol_filter::forcing_rows: rows of mp, padding zero)
 struct ForcingDev {
-    ForcingPlan plan;
-    double* table = nullptr;    // device: cap rows of mp, padding zero
-    int* words = nullptr;       // device: [plan.next of the running call, plan.count], written once per call (k_force_cursor)
-    int cap = 0;
     double* fshift = nullptr;   // device, mp: the shift a forced step measures with
     double* h_one = nullptr;    // mapped host memory, mp: the right-hand side of pnmol_filter_force_at
     double* h_one_dev = nullptr;
@@ -51,11 +47,6 @@ __global__ __launch_bounds__(256) void k_force(const double* __restrict__ rhs, c
     fshift[i] = i < m ? shift[i] - rhs[r * mp + i] : 0.0;
 }
 
-__global__ void k_force_cursor(int* __restrict__ words, int next, int count) {
-    words[0] = next;
-    words[1] = count;
-}
-
 int refuse(pnmol_filter* f, const char* who, const std::string& why) {
     f->ctx->err = std::string(who) + why;
     return -1;
@@ -68,8 +59,6 @@ int ensure_dev(pnmol_filter* f, const char* who) {
     const size_t row = sizeof(double) * (size_t)f->mp;
     hipError_t e = hipMalloc(&v->fshift, row);
     if (e == hipSuccess) e = hipMemset(v->fshift, 0, row);
-    if (e == hipSuccess) e = hipMalloc(&v->words, 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(v->words, 0, 2 * sizeof(int));
     if (e == hipSuccess) e = hipHostMalloc(&v->h_one, row, hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&v->h_one_dev), v->h_one, 0);
     if (e == hipSuccess) e = hipEventCreate(&v->ev_one);
@@ -97,38 +86,21 @@ int enqueue_force(pnmol_filter* f, const double* rhs, const int* words, const in
 void pnmol_forcing_free(pnmol_filter* f) {
     ForcingDev* v = f->forcing;
     if (!v) return;
-    for (void* q : {(void*)v->table, (void*)v->words, (void*)v->fshift})
-        if (q) (void)hipFree(q);
+    if (v->fshift) (void)hipFree(v->fshift);
     if (v->h_one) (void)hipHostFree(v->h_one);
     if (v->ev_one) (void)hipEventDestroy(v->ev_one);
     delete v;
     f->forcing = nullptr;
 }
 
-bool pnmol_forcing_table_set(const pnmol_filter* f) { return f->forcing && f->forcing->plan.set(); }
-bool pnmol_forcing_set(const pnmol_filter* f) { return f->forcing && (f->forcing->plan.set() || f->forcing->single); }
-
-int pnmol_forcing_begin(pnmol_filter* f, int k) {
-    if (!f->forcing) return 0;
-    const std::string why = forcing_plan_begin(f->forcing->plan, k);
-    if (why.empty()) return 0;
-    f->ctx->err = "pnmol_filter_steps_begin: forcing: " + why;
-    return -1;
-}
-
-int pnmol_forcing_enqueue_cursor(pnmol_filter* f) {
-    if (!pnmol_forcing_table_set(f)) return 0;
-    ForcingDev* v = f->forcing;
-    k_force_cursor<<<1, 1, 0, f->ctx->stream>>>(v->words, v->plan.next, v->plan.count);
-    HIPCHK(f->ctx, hipGetLastError());
-    return 0;
-}
+bool pnmol_forcing_table_set(const pnmol_filter* f) { return f->forcing_rows.plan.set(); }
+bool pnmol_forcing_set(const pnmol_filter* f) { return pnmol_forcing_table_set(f) || (f->forcing && f->forcing->single); }
 
 const double* pnmol_forcing_enqueue_loop(pnmol_filter* f, int* rc) {
     *rc = 0;
     if (!pnmol_forcing_table_set(f)) return nullptr;
     ForcingDev* v = f->forcing;
-    *rc = enqueue_force(f, v->table, v->words, f->ctr);
+    *rc = enqueue_force(f, f->forcing_rows.rows, f->forcing_rows.words, f->ctr);
     return v->fshift;
 }
 
@@ -144,16 +116,6 @@ const double* pnmol_forcing_enqueue_single(pnmol_filter* f, int* rc) {
     return v->fshift;
 }
 
-void pnmol_forcing_collect(pnmol_filter* f, int k, bool ok) {
-    if (f->forcing) forcing_plan_collect(&f->forcing->plan, k, ok);
-}
-
-int pnmol_forcing_cursor(const pnmol_filter* f) { return f->forcing ? f->forcing->plan.next : 0; }
-
-void pnmol_forcing_rewind(pnmol_filter* f, int next) {
-    if (f->forcing) forcing_plan_rewind(&f->forcing->plan, next);
-}
-
 extern "C" {
 
 int pnmol_filter_set_forcing(pnmol_filter* f, int count, const double* rhs_cm) {
@@ -164,19 +126,12 @@ int pnmol_filter_set_forcing(pnmol_filter* f, int count, const double* rhs_cm) {
     if (!why.empty()) return refuse(f, who, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a launch that reads the table may still be in flight)
-    pnmol_drop_graphs(f);  // (the loop's launch sequence differs with and without a table)
     if (count == 0 || !rhs_cm) {
-        if (f->forcing) {
-            if (f->forcing->table) (void)hipFree(f->forcing->table);
-            f->forcing->table = nullptr, f->forcing->cap = 0;
-            f->forcing->plan = ForcingPlan{};
-            if (!f->forcing->single) pnmol_forcing_free(f);
-        }
+        loop_table_clear(f, &f->forcing_rows);
+        if (f->forcing && !f->forcing->single) pnmol_forcing_free(f);
         return 0;
     }
     if (int rc = ensure_dev(f, who)) return rc;
-    ForcingDev* v = f->forcing;
-    const size_t bytes = sizeof(double) * (size_t)count * (size_t)f->mp;
     std::vector<double> pad;
     try {
         pad.resize((size_t)count * (size_t)f->mp);
@@ -185,32 +140,12 @@ int pnmol_filter_set_forcing(pnmol_filter* f, int count, const double* rhs_cm) {
         return -4;
     }
     forcing_plan_pad(rhs_cm, count, f->m, f->mp, pad.data());
-    if (count > v->cap) {
-        double* fresh = nullptr;
-        const hipError_t e = hipMalloc(&fresh, bytes);
-        if (e != hipSuccess) {  // (nothing is installed: the table set before, if any, stays as it was)
-            ctx->err = std::string(who) + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? -4 : -2;
-        }
-        if (v->table) (void)hipFree(v->table);
-        v->table = fresh, v->cap = count;
-        v->plan = ForcingPlan{};
-    }
-    const hipError_t e = hipMemcpy(v->table, pad.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {  // (the table is half overwritten: no table is left set)
-        ctx->err = std::string(who) + hipGetErrorString(e);
-        v->plan = ForcingPlan{};
-        return -2;
-    }
-    forcing_plan_fill(&v->plan, count, rhs_cm);
-    return 0;
+    // (a table that fits is overwritten in place and the captured graphs replay on it: they address it through the words)
+    return loop_table_install(f, &f->forcing_rows, who, count, f->mp, pad.data());
 }
 
 int pnmol_filter_forcing_pending(const pnmol_filter* f, int* next, int* count) {
-    if (!f) return -1;
-    if (next) *next = f->forcing ? f->forcing->plan.next : 0;
-    if (count) *count = f->forcing ? f->forcing->plan.count : 0;
-    return 0;
+    return f ? loop_table_pending(f->forcing_rows, next, count) : -1;
 }
 
 int pnmol_filter_force_at(pnmol_filter* f, const double* rhs_m) {

@@ -3890,6 +3890,7 @@ int pnmol_filter_destroy(pnmol_filter* f) {
     pnmol_reaction_free_ws(f);
     pnmol_forcing_free(f);
     pnmol_operator_free(f);
+    loop_tables_free(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     delete f;
@@ -4115,14 +4116,9 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     // a recorder: enough slots left and s not among them -- or the refusal, before anything is enqueued
     int rc = pnmol_record_begin(f, s, k);
     if (rc != 0) return rc;
-    // a table of linearisation points: enough rows left -- or the refusal, before anything is enqueued
-    rc = pnmol_linearize_begin(f, k);
-    if (rc != 0) return rc;
-    // a table of right-hand sides: the same
-    rc = pnmol_forcing_begin(f, k);
-    if (rc != 0) return rc;
-    // a schedule of operator coefficients: the same
-    rc = pnmol_operator_begin(f, k);
+    // the per-step tables (linearisation points, right-hand sides, operator coefficients): enough rows left in each -- or the
+    // refusal, before anything is enqueued
+    rc = loop_tables_begin(f, k);
     if (rc != 0) return rc;
     // a sensor plan: which entry goes behind which step of this call -- or the refusal, before anything is enqueued
     std::vector<int> ob_entry;
@@ -4139,9 +4135,7 @@ int pnmol_filter_steps_begin(pnmol_filter* f, pnmol_state* s, int k, double dt) 
     hipStream_t st = ctx->stream;
     k_init_call<<<1, 256, 0, st>>>(f->info, k, f->ctr, f->last_ctr);
     if ((rc = pnmol_record_enqueue_cursor(f)) != 0) return rc;
-    if ((rc = pnmol_linearize_enqueue_cursor(f)) != 0) return rc;
-    if ((rc = pnmol_forcing_enqueue_cursor(f)) != 0) return rc;
-    if ((rc = pnmol_operator_enqueue_cursor(f)) != 0) return rc;
+    if ((rc = loop_tables_enqueue_cursors(f)) != 0) return rc;
     if (pnmol_operator_schedule_set(f)) f->sq_dt = -1.0;  // H changes with every step: no error model either
     if (has_term(f)) f->sq_dt = -1.0;  // Sq^-1 belongs to one linearisation: the loop runs without an error model
     const bool fused = fused_loop(f);
@@ -4259,10 +4253,8 @@ int pnmol_filter_steps_end(pnmol_filter* f, pnmol_state* s, double* means_kd, do
     // in time, so a step's own error at or before j takes precedence.
     int ob_step = -1;
     const int ob_rc = pnmol_observe_plan_collect(f, &ob_step);
-    // a table of linearisation points: the call's rows are consumed, unless it failed (the cursor then stays where the call began)
-    pnmol_linearize_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);
-    pnmol_forcing_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);  // (a table of right-hand sides: the same rule)
-    pnmol_operator_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);  // (a schedule of operator coefficients: the same)
+    // the per-step tables: the call's rows are consumed, unless it failed (the cursors then stay where the call began)
+    loop_tables_collect(f, k, ob_rc == 0 && stuck < 0 && bad < 0);
     if (ob_rc != 0) {
         const int first = stuck >= 0 && (bad < 0 || stuck < bad) ? stuck : bad;  // the first step that failed by itself
         if (first < 0 || first > ob_step) return ob_rc;                         // (ctx->err names entry, pivot and step)
@@ -4304,15 +4296,11 @@ int pnmol_filter_prepare_steps(pnmol_filter* f, pnmol_state* s, int k, double dt
     if (e == hipSuccess) {
         const int ob_next = pnmol_observe_plan_cursor(f);  // (a sensor plan: the rehearsal applies entries; the cursor goes back)
         const int rec_next = pnmol_record_cursor(f);       // (a recorder: the rehearsal fills slots the real call fills again)
-        const int lin_next = pnmol_linearize_cursor(f);    // (linearisation points: the rehearsal consumes rows of the real call)
-        const int frc_next = pnmol_forcing_cursor(f);      // (right-hand sides: the same)
-        const int opr_next = pnmol_operator_cursor(f);     // (operator coefficients: the same)
+        const LoopCursors tab_next = loop_tables_cursors(f);  // (the per-step tables: the rehearsal consumes rows of the real call)
         rc = pnmol_filter_steps(f, s, k, dt, nullptr, nullptr, nullptr);
         pnmol_observe_plan_rewind(f, ob_next);
         pnmol_record_rewind(f, rec_next);
-        pnmol_linearize_rewind(f, lin_next);
-        pnmol_forcing_rewind(f, frc_next);
-        pnmol_operator_rewind(f, opr_next);
+        loop_tables_rewind(f, tab_next);
         if (rc == -3) rc = 0;  // a non-PD rehearsal is reported by the real call
         if ((k & 1) && rc == 0) {  // odd k swapped buffer ownership: swap back so the cached graphs stay valid
             double* t;

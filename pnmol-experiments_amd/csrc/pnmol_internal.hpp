@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "pnmol_cursor_plan.hpp"
 #include "pnmol_hip.h"
 #include "pnmol_observe_plan.hpp"  // (times_agree lives there: the plan's walk uses it without anything of HIP)
 
@@ -93,6 +94,13 @@ struct TermImage {
     int w = 0, slot_rows = 0;
     TermKind kind = TermKind::none;  // what it was built for
     int ncomp = 0;
+};
+
+// one of the filter's per-step tables (LoopTable, pnmol_cursor_plan.hpp) and what the refusal of a call names it and its rows
+constexpr int LOOP_TABLES = 3;
+struct LoopTableRef {
+    LoopTable* tab;
+    LoopTableName name;
 };
 
 struct pnmol_filter {
@@ -210,18 +218,22 @@ struct pnmol_filter {
     // reaction leave it alone); a convection term rebuilds it with every set call (G comes with the term), and so does a system set
     // after a convection term -- one more cold setter call than when each kind kept an image of its own.
     TermImage term_img;
-    // Linearisation points of the constant-step loop (pnmol_filter_set_linearization_points, pnmol_reaction.hip): NULL = none, every
-    // step is linearised at its own predicted mean.  While a table is set the i-th step taken since is linearised at its row i.
-    struct LinearizeDev* lin_plan = nullptr;
-    // Driven problems (pnmol_filter_set_forcing, pnmol_filter_force_at, pnmol_forcing.hip): NULL = none.  While a table is set the
-    // constant-step loop runs non-fused and its i-th step taken since measures against row i; a forced step reads its shift from a
-    // buffer of the forcing's own, so `shift` stays what the operator setters and the term kernels made it.
+    // Driven problems (pnmol_filter_set_forcing, pnmol_filter_force_at, pnmol_forcing.hip): NULL = none.  A forced step reads its
+    // shift from a buffer of the forcing's own, so `shift` stays what the operator setters and the term kernels made it.
     struct ForcingDev* forcing = nullptr;
     // A time-dependent operator M(t) = sum_r a_r(t) L_r (pnmol_filter_set_operator_family, pnmol_operator.hip): NULL = none.  While
     // a family is set ell_col / ell_val hold its union image, the operator setters and the terms with an image of their own refuse,
-    // and a pointwise reaction linearises on the family's current operator.  While a schedule of coefficients is set as well the
-    // constant-step loop runs non-fused, without an error model, and its i-th step taken since runs with row i.
+    // and a pointwise reaction linearises on the family's current operator.
     struct OperatorDev* op_family = nullptr;
+    // The per-step tables of the constant-step loop (pnmol_loop_table.hip): while one is set the i-th step taken since consumes its
+    // row i.  lin_points (pnmol_filter_set_linearization_points): the step is linearised at the row instead of its own predicted
+    // mean; the table belongs to the term and goes with it.  forcing_rows (pnmol_filter_set_forcing): the step measures against
+    // the row.  op_schedule (pnmol_filter_set_operator_schedule): the step runs with the operator of the row's coefficients; the
+    // table belongs to the family and goes with it.  With forcing_rows or op_schedule set the loop runs non-fused, with op_schedule
+    // also without an error model.  loop_tables: all of them, in the order in which pnmol_filter_steps_begin refuses.
+    LoopTable lin_points, forcing_rows, op_schedule;
+    const LoopTableRef loop_tables[LOOP_TABLES] = {
+        {&lin_points, LOOP_POINTS}, {&forcing_rows, LOOP_FORCING}, {&op_schedule, LOOP_SCHEDULE}};
     // Linear functionals of the trajectory (pnmol_functionals, pnmol_functional.hip): the workspace of the pass, allocated on first use
     struct FunctionalWs* fn_ws = nullptr;
 };
@@ -346,15 +358,6 @@ void pnmol_reaction_free_ws(pnmol_filter* f);
 // the device words name (the cursor word of the running call plus the loop's step counter; outside the loop those words name
 // nothing, so pnmol_filter_linearize passes false).  Needs has_term(f); no synchronisation.  -2: the launch failed.
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt, bool loop_step);
-// pnmol_reaction.hip: the table of linearisation points inside pnmol_filter_steps_begin / _end, as the recorder's functions above:
-// the refusal of a call of k steps (-1, ctx->err set; nothing of HIP is touched), the cursor words of the running call on the ctx
-// stream (once per call, in front of its steps), behind the call's synchronisation the cursor moves (ok) or stays (the call
-// failed), and the cursor and putting it back for a rehearsal.
-int pnmol_linearize_begin(pnmol_filter* f, int k);
-int pnmol_linearize_enqueue_cursor(pnmol_filter* f);
-void pnmol_linearize_collect(pnmol_filter* f, int k, bool ok);
-int pnmol_linearize_cursor(const pnmol_filter* f);
-void pnmol_linearize_rewind(pnmol_filter* f, int next);
 // pnmol_forcing.hip: the forcing inside pnmol_filter_step and pnmol_filter_steps_begin / _end.  table_set: a table of right-hand
 // sides is set (the loop then runs non-fused: the next innovation cannot be prepared before its right-hand side is in place); set: a
 // table, or a right-hand side of pnmol_filter_force_at (the operator setters then refuse).
@@ -365,12 +368,6 @@ bool pnmol_forcing_set(const pnmol_filter* f);
 // table / a right-hand side (nothing is enqueued then: the step reads f->shift as ever).  *rc = -2: the launch failed.
 const double* pnmol_forcing_enqueue_loop(pnmol_filter* f, int* rc);
 const double* pnmol_forcing_enqueue_single(pnmol_filter* f, int* rc);
-// the table inside a call, as the table of linearisation points above: refusal of k steps, cursor words, collect, cursor and rewind
-int pnmol_forcing_begin(pnmol_filter* f, int k);
-int pnmol_forcing_enqueue_cursor(pnmol_filter* f);
-void pnmol_forcing_collect(pnmol_filter* f, int k, bool ok);
-int pnmol_forcing_cursor(const pnmol_filter* f);
-void pnmol_forcing_rewind(pnmol_filter* f, int next);
 void pnmol_forcing_free(pnmol_filter* f);
 // pnmol_operator.hip: the time-dependent operator.  family_set: the operator setters and the wide terms refuse; schedule_set: a table
 // of coefficients is set (the loop then runs non-fused: the next step's H is not in place before its row has been applied).
@@ -385,13 +382,29 @@ int pnmol_operator_put_image(pnmol_filter* f);
 // k_operator_at in front of a step of the loop (the row the device words name), on the ctx stream, in front of the step's linearise
 // launch.  Without a schedule nothing is enqueued.  -2: the launch failed.
 int pnmol_operator_enqueue_loop(pnmol_filter* f);
-// the table inside a call, as the table of right-hand sides above: refusal of k steps, cursor words, collect, cursor and rewind
-int pnmol_operator_begin(pnmol_filter* f, int k);
-int pnmol_operator_enqueue_cursor(pnmol_filter* f);
-void pnmol_operator_collect(pnmol_filter* f, int k, bool ok);
-int pnmol_operator_cursor(const pnmol_filter* f);
-void pnmol_operator_rewind(pnmol_filter* f, int next);
 void pnmol_operator_free(pnmol_filter* f);
+// pnmol_loop_table.hip: the per-step tables (pnmol_filter::loop_tables).  A setter has validated and padded its rows and synchronised
+// the stream; install uploads `count` rows of `stride` doubles: a table that fits the one before it is overwritten in place, one
+// that does not is allocated first and swapped in only if that succeeded, a failed copy leaves no table set, and the captured
+// graphs go or stay as loop_table_change says.  -4: out of memory, -2: another failure, ctx->err = who + the HIP error.  clear
+// frees a table (its graphs go with it); free clears them all (pnmol_filter_destroy).
+int loop_table_install(pnmol_filter* f, LoopTable* tab, const char* who, int count, int stride, const double* padded_rows);
+void loop_table_clear(pnmol_filter* f, LoopTable* tab);
+void loop_tables_free(pnmol_filter* f);
+// what the pnmol_filter_*_pending functions report of a table
+int loop_table_pending(const LoopTable& tab, int* next, int* count);
+// the tables inside pnmol_filter_steps_begin / _end, as the recorder's functions above: the first refusal of a call of k steps in
+// list order (-1, ctx->err set; nothing of HIP is touched), the cursor words of the running call on the ctx stream (once per call,
+// in front of its steps), behind the call's synchronisation the cursors move (ok) or stay (the call failed), and the cursors and
+// putting them back for a rehearsal.
+int loop_tables_begin(pnmol_filter* f, int k);
+int loop_tables_enqueue_cursors(pnmol_filter* f);
+void loop_tables_collect(pnmol_filter* f, int k, bool ok);
+struct LoopCursors {
+    int next[LOOP_TABLES];
+};
+LoopCursors loop_tables_cursors(const pnmol_filter* f);
+void loop_tables_rewind(pnmol_filter* f, const LoopCursors& c);
 // pnmol_hip.hip: destroy the captured graphs of the constant-step loop
 void pnmol_drop_graphs(pnmol_filter* f);
 // pnmol_hip.hip: make ell_col / ell_val at least w slots wide.  Growing frees them (ellw = 0 until the caller has filled them): the

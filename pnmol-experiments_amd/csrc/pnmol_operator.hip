@@ -22,7 +22,8 @@
 
 static_assert(OPERATOR_MAXR == PNMOL_OPERATOR_MAXR, "the plan header and the C ABI agree on the number of operators");
 
-// host logic in pnmol_operator_plan.hpp; image, planes, rows and words live on the device
+// host logic in pnmol_operator_plan.hpp; image and planes live on the device.  The schedule is the loop's table
+// pnmol_filter::op_schedule (rows of OPERATOR_MAXR, padding zero), which goes with the family it was set for.
 struct OperatorDev {
     int R = 0, w = 0;
     int* col = nullptr;          // w x mp: the union image's columns
@@ -32,10 +33,6 @@ struct OperatorDev {
     int* slot = nullptr;         // mp: the diagonal slot of every PDE row
     double* cur = nullptr;       // w x mp: the current operator, as ell_val holds it without a reaction's diagonal
     double* rdiag0 = nullptr;    // mp: the noise given at creation
-    OperatorPlan plan;
-    double* table = nullptr;     // device: cap rows of OPERATOR_MAXR, padding zero
-    int* words = nullptr;        // device: [plan.next of the running call, plan.count], written once per call
-    int cap = 0;
     double* h_one = nullptr;     // mapped host memory, OPERATOR_MAXR: the coefficients of pnmol_filter_operator_at
     double* h_one_dev = nullptr;
     hipEvent_t ev_one = nullptr;  // behind the last launch that read h_one
@@ -93,11 +90,6 @@ __global__ __launch_bounds__(256) void k_operator_at(const double* __restrict__ 
     }
 }
 
-__global__ void k_operator_cursor(int* __restrict__ words, int next, int count) {
-    words[0] = next;
-    words[1] = count;
-}
-
 int refuse(pnmol_filter* f, const char* who, const std::string& why) {
     f->ctx->err = std::string(who) + why;
     return -1;
@@ -132,8 +124,7 @@ hipError_t upload(T** dst, const std::vector<T>& src) {
 
 void free_dev(OperatorDev* v) {
     if (!v) return;
-    for (void* q : {(void*)v->col, (void*)v->val, (void*)v->planes, (void*)v->e, (void*)v->slot, (void*)v->cur, (void*)v->rdiag0,
-                    (void*)v->table, (void*)v->words})
+    for (void* q : {(void*)v->col, (void*)v->val, (void*)v->planes, (void*)v->e, (void*)v->slot, (void*)v->cur, (void*)v->rdiag0})
         if (q) (void)hipFree(q);
     if (v->h_one) (void)hipHostFree(v->h_one);
     if (v->ev_one) (void)hipEventDestroy(v->ev_one);
@@ -157,7 +148,7 @@ void pnmol_operator_free(pnmol_filter* f) {
 }
 
 bool pnmol_operator_family_set(const pnmol_filter* f) { return f->op_family != nullptr; }
-bool pnmol_operator_schedule_set(const pnmol_filter* f) { return f->op_family && f->op_family->plan.set(); }
+bool pnmol_operator_schedule_set(const pnmol_filter* f) { return f->op_schedule.plan.set(); }
 
 void pnmol_operator_linearize_base(const pnmol_filter* f, const double** base_val, const int** slot) {
     if (!f->op_family) return;
@@ -180,36 +171,9 @@ int pnmol_operator_put_image(pnmol_filter* f) {
     return 0;
 }
 
-int pnmol_operator_begin(pnmol_filter* f, int k) {
-    if (!f->op_family) return 0;
-    const std::string why = operator_plan_begin(f->op_family->plan, k);
-    if (why.empty()) return 0;
-    f->ctx->err = "pnmol_filter_steps_begin: operator schedule: " + why;
-    return -1;
-}
-
-int pnmol_operator_enqueue_cursor(pnmol_filter* f) {
-    if (!pnmol_operator_schedule_set(f)) return 0;
-    OperatorDev* v = f->op_family;
-    k_operator_cursor<<<1, 1, 0, f->ctx->stream>>>(v->words, v->plan.next, v->plan.count);
-    HIPCHK(f->ctx, hipGetLastError());
-    return 0;
-}
-
 int pnmol_operator_enqueue_loop(pnmol_filter* f) {
     if (!pnmol_operator_schedule_set(f)) return 0;
-    OperatorDev* v = f->op_family;
-    return enqueue_operator(f, v->table, v->words, f->ctr);
-}
-
-void pnmol_operator_collect(pnmol_filter* f, int k, bool ok) {
-    if (f->op_family) operator_plan_collect(&f->op_family->plan, k, ok);
-}
-
-int pnmol_operator_cursor(const pnmol_filter* f) { return f->op_family ? f->op_family->plan.next : 0; }
-
-void pnmol_operator_rewind(pnmol_filter* f, int next) {
-    if (f->op_family) operator_plan_rewind(&f->op_family->plan, next);
+    return enqueue_operator(f, f->op_schedule.rows, f->op_schedule.words, f->ctr);
 }
 
 extern "C" {
@@ -230,6 +194,7 @@ int pnmol_filter_set_operator_family(pnmol_filter* f, int R, const double* L_Rdd
         const int rc = restore_plain(f, old);
         if (rc == 0) (void)hipStreamSynchronize(ctx->stream);  // (the copy above reads old->rdiag0)
         free_dev(old);
+        loop_table_clear(f, &f->op_schedule);  // (its schedule goes with it)
         return rc;
     }
     const int d = f->d, mp = f->mp, bw = f->base_w;
@@ -256,8 +221,6 @@ int pnmol_filter_set_operator_family(pnmol_filter* f, int R, const double* L_Rdd
     if (e == hipSuccess) e = hipMalloc(&v->rdiag0, row);
     // the noise given at creation: f->rdiag holds it unless a family is being replaced
     if (e == hipSuccess) e = hipMemcpy(v->rdiag0, f->op_family ? f->op_family->rdiag0 : f->rdiag, row, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMalloc(&v->words, 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(v->words, 0, 2 * sizeof(int));
     if (e == hipSuccess) e = hipHostMalloc(&v->h_one, sizeof(double) * OPERATOR_MAXR, hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&v->h_one_dev), v->h_one, 0);
     if (e == hipSuccess) e = hipEventCreate(&v->ev_one);
@@ -272,7 +235,8 @@ int pnmol_filter_set_operator_family(pnmol_filter* f, int R, const double* L_Rdd
     int rc = pnmol_operator_put_image(f);
     if (rc == 0) rc = hipMemcpyAsync(f->rdiag, v->rdiag0, row, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess ? 0 : -2;
     if (rc == 0) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? 0 : -2;
-    free_dev(old);  // (its schedule goes with it)
+    free_dev(old);
+    loop_table_clear(f, &f->op_schedule);  // (the schedule of the family before goes with it)
     f->sq_dt = -1.0;  // the error model belongs to the operator that was set
     if (rc != 0) {  // no half-installed family: the operator given at creation
         const std::string err = ctx->err.empty() ? std::string(who) + "installing the image failed" : ctx->err;
@@ -294,19 +258,10 @@ int pnmol_filter_set_operator_schedule(pnmol_filter* f, int count, const double*
     if (!why.empty()) return refuse(f, who, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a launch that reads the table may still be in flight)
-    // the loop's launch sequence differs with and without a table, and the launches hold the table's address: a table that fits
-    // the one before it is overwritten in place and the captured graphs replay on it
-    const bool in_place = count > 0 && a_cR && v->plan.set() && count <= v->cap;
-    if (!in_place) pnmol_drop_graphs(f);
     if (count == 0 || !a_cR) {
-        if (v) {
-            if (v->table) (void)hipFree(v->table);
-            v->table = nullptr, v->cap = 0;
-            v->plan = OperatorPlan{};
-        }
+        loop_table_clear(f, &f->op_schedule);
         return 0;
     }
-    const size_t bytes = sizeof(double) * (size_t)count * OPERATOR_MAXR;
     std::vector<double> pad;
     try {
         pad.resize((size_t)count * OPERATOR_MAXR);
@@ -315,32 +270,12 @@ int pnmol_filter_set_operator_schedule(pnmol_filter* f, int count, const double*
         return -4;
     }
     operator_schedule_pad(a_cR, count, v->R, pad.data());
-    if (count > v->cap) {
-        double* fresh = nullptr;
-        const hipError_t e = hipMalloc(&fresh, bytes);
-        if (e != hipSuccess) {  // (nothing is installed: the table set before, if any, stays as it was)
-            ctx->err = std::string(who) + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? -4 : -2;
-        }
-        if (v->table) (void)hipFree(v->table);
-        v->table = fresh, v->cap = count;
-        v->plan = OperatorPlan{};
-    }
-    const hipError_t e = hipMemcpy(v->table, pad.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {  // (the table is half overwritten: no table is left set)
-        ctx->err = std::string(who) + hipGetErrorString(e);
-        v->plan = OperatorPlan{};
-        return -2;
-    }
-    operator_plan_fill(&v->plan, count, a_cR);
-    return 0;
+    // (a table that fits is overwritten in place and the captured graphs replay on it: they address it through the words)
+    return loop_table_install(f, &f->op_schedule, who, count, OPERATOR_MAXR, pad.data());
 }
 
 int pnmol_filter_operator_schedule_pending(const pnmol_filter* f, int* next, int* count) {
-    if (!f) return -1;
-    if (next) *next = f->op_family ? f->op_family->plan.next : 0;
-    if (count) *count = f->op_family ? f->op_family->plan.count : 0;
-    return 0;
+    return f ? loop_table_pending(f->op_schedule, next, count) : -1;
 }
 
 int pnmol_filter_operator_at(pnmol_filter* f, const double* a_R) {

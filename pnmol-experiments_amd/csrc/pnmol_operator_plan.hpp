@@ -1,7 +1,8 @@
 // pnmol_operator_plan.hpp -- host side of a time-dependent operator M(t) = sum_r a_r(t) L_r (pnmol_filter_set_operator_family,
 // pnmol_filter_set_operator_schedule, pnmol_filter_operator_at; pnmol_operator.hip): validation of a family and of a table of
-// coefficients, the union image of the L_r with its value planes, and the cursor of the table, which is that of every table of the
-// loop (pnmol_cursor_plan.hpp).  Nothing of HIP in here: tests/operator_plan_check.cpp builds it on its own under the sanitizers.
+// coefficients, its padded image and the union image of the L_r with its value planes.  The table itself and its cursor are those of
+// every table of the loop (pnmol_cursor_plan.hpp).  Nothing of HIP in here: tests/operator_plan_check.cpp builds it on its own under
+// the sanitizers.
 #pragma once
 #include <cmath>
 #include <string>
@@ -12,8 +13,6 @@
 #include "pnmol_term_image.hpp"
 
 constexpr int OPERATOR_MAXR = 4;  // (PNMOL_OPERATOR_MAXR, include/pnmol_hip.h)
-
-using OperatorPlan = CursorPlan;  // next: the row of coefficients the next step taken runs with
 
 // what the filter says of itself to the three setters
 struct OperatorFilterFacts {
@@ -89,12 +88,6 @@ inline void operator_schedule_pad(const double* a, int count, int R, double* out
     for (long r = 0; r < count; ++r)
         for (long j = 0; j < OPERATOR_MAXR; ++j) out[r * OPERATOR_MAXR + j] = j < R ? a[r * R + j] : 0.0;
 }
-
-inline void operator_plan_fill(OperatorPlan* p, int count, const double* a) { cursor_plan_fill(p, count, a != nullptr); }
-inline std::string operator_plan_begin(const OperatorPlan& p, int k) { return cursor_plan_begin(p, k, "row(s) of coefficients"); }
-inline int operator_plan_row(const OperatorPlan& p, int j) { return cursor_plan_row(p, j); }
-inline void operator_plan_collect(OperatorPlan* p, int k, bool ok) { cursor_plan_collect(p, k, ok); }
-inline void operator_plan_rewind(OperatorPlan* p, int next) { cursor_plan_rewind(p, next); }
 
 // The union image of a family: the base image (boundary rows, padding and the base values of its own columns) with a slot in every
 // PDE row for each column in which any L_r has an entry, and for the diagonal.  Never a function of the coefficients: an operator

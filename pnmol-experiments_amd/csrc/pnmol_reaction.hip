@@ -33,15 +33,6 @@
 #include "pnmol_linearize_plan.hpp"
 #include "pnmol_term_image.hpp"
 
-// The table of linearisation points of the constant-step loop (pnmol_filter_set_linearization_points): host logic in
-// pnmol_linearize_plan.hpp; the rows and the two words the kernels address them by live on the device, as the recorder's slots do.
-struct LinearizeDev {
-    LinearizePlan plan;
-    double* table = nullptr;  // device: cap rows of d
-    int* words = nullptr;     // device: [plan.next of the running call, plan.count], written once per call (k_linearize_cursor)
-    int cap = 0;
-};
-
 namespace {
 
 // what a kernel needs to form the predicted mean from the step's input mean
@@ -374,16 +365,6 @@ void free_term_image(pnmol_filter* f) {
     im = TermImage{};
 }
 
-// (the caller knows the stream idle or the table out of use, and has dropped the graphs that address it)
-void free_linearize_table(pnmol_filter* f) {
-    LinearizeDev* l = f->lin_plan;
-    if (!l) return;
-    for (void* q : {(void*)l->table, (void*)l->words})
-        if (q) (void)hipFree(q);
-    delete l;
-    f->lin_plan = nullptr;
-}
-
 template <class T>
 int upload(pnmol_ctx* ctx, T** dst, const std::vector<T>& src) {
     if (src.empty()) return 0;
@@ -441,9 +422,9 @@ int put_term_image(pnmol_filter* f, TermKind kind, int ncomp, const double* G) {
 // A table of linearisation points belongs to the term it was set for: it goes with it.
 int install_term(pnmol_filter* f, TermKind kind, int ncomp = 0, const double* G = nullptr) {
     pnmol_drop_graphs(f);
-    if (f->lin_plan) {
+    if (f->lin_points.rows) {
         HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (a launch that reads the table may still be in flight)
-        free_linearize_table(f);
+        loop_table_clear(f, &f->lin_points);
     }
     const bool image = kind == TermKind::system || kind == TermKind::convection;
     // (a time-dependent operator, pnmol_operator.hip: its image with the current operator is what a pointwise reaction patches)
@@ -498,49 +479,18 @@ int enqueue_linearize(pnmol_filter* f, const double* mean, double frame_dt, doub
     return 0;
 }
 
-__global__ void k_linearize_cursor(int* __restrict__ words, int next, int count) {
-    words[0] = next;
-    words[1] = count;
-}
-
 }  // namespace
 
 void pnmol_reaction_free_ws(pnmol_filter* f) {
     free_term_image(f);
-    free_linearize_table(f);
 }
 
 int pnmol_reaction_enqueue(pnmol_filter* f, const double* mean, double frame_dt, double dt, bool loop_step) {
     // only a step of the loop takes its point from the table: the words that name the row belong to the running call
-    const LinearizeDev* l = loop_step ? f->lin_plan : nullptr;
-    const PointSource pt = l ? PointSource{l->table, l->words, f->ctr, f->d} : PointSource{nullptr, nullptr, nullptr, f->d};
+    const LoopTable& l = f->lin_points;
+    const PointSource pt = loop_step && l.plan.set() ? PointSource{l.rows, l.words, f->ctr, f->d}
+                                                     : PointSource{nullptr, nullptr, nullptr, f->d};
     return enqueue_linearize(f, mean, frame_dt, dt, pt);
-}
-
-int pnmol_linearize_begin(pnmol_filter* f, int k) {
-    if (!f->lin_plan) return 0;
-    const std::string why = linearize_plan_begin(f->lin_plan->plan, k);
-    if (why.empty()) return 0;
-    f->ctx->err = "pnmol_filter_steps_begin: linearisation points: " + why;
-    return -1;
-}
-
-int pnmol_linearize_enqueue_cursor(pnmol_filter* f) {
-    LinearizeDev* l = f->lin_plan;
-    if (!l) return 0;
-    k_linearize_cursor<<<1, 1, 0, f->ctx->stream>>>(l->words, l->plan.next, l->plan.count);
-    HIPCHK(f->ctx, hipGetLastError());
-    return 0;
-}
-
-void pnmol_linearize_collect(pnmol_filter* f, int k, bool ok) {
-    if (f->lin_plan) linearize_plan_collect(&f->lin_plan->plan, k, ok);
-}
-
-int pnmol_linearize_cursor(const pnmol_filter* f) { return f->lin_plan ? f->lin_plan->plan.next : 0; }
-
-void pnmol_linearize_rewind(pnmol_filter* f, int next) {
-    if (f->lin_plan) linearize_plan_rewind(&f->lin_plan->plan, next);
 }
 
 extern "C" {
@@ -554,48 +504,15 @@ int pnmol_filter_set_linearization_points(pnmol_filter* f, int count, const doub
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a launch that reads the table may still be in flight)
     if (count == 0 || !u_cd) {
-        if (f->lin_plan) {
-            pnmol_drop_graphs(f);  // (the loop's linearise launches take another argument with a table)
-            free_linearize_table(f);
-        }
+        loop_table_clear(f, &f->lin_points);
         return 0;
     }
-    LinearizeDev* l = f->lin_plan;
-    if (!l || count > l->cap) {  // (a table that fits is overwritten in place: the captured graphs address it through the words)
-        LinearizeDev* fresh = new LinearizeDev();
-        hipError_t e = hipMalloc(&fresh->table, sizeof(double) * (size_t)count * (size_t)f->d);
-        if (e == hipSuccess) e = hipMalloc(&fresh->words, 2 * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(fresh->words, 0, 2 * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpy(fresh->table, u_cd, sizeof(double) * (size_t)count * (size_t)f->d, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {  // (nothing is installed: the table set before, if any, stays as it was)
-            ctx->err = std::string(who) + hipGetErrorString(e);
-            for (void* q : {(void*)fresh->table, (void*)fresh->words})
-                if (q) (void)hipFree(q);
-            delete fresh;
-            return e == hipErrorOutOfMemory ? -4 : -2;
-        }
-        fresh->cap = count;
-        pnmol_drop_graphs(f);
-        free_linearize_table(f);
-        f->lin_plan = l = fresh;
-    } else {
-        const hipError_t e = hipMemcpy(l->table, u_cd, sizeof(double) * (size_t)count * (size_t)f->d, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {  // (the table is half overwritten: no table is left set)
-            ctx->err = std::string(who) + hipGetErrorString(e);
-            pnmol_drop_graphs(f);
-            free_linearize_table(f);
-            return -2;
-        }
-    }
-    linearize_plan_fill(&l->plan, count, u_cd);
-    return 0;
+    // (a table that fits is overwritten in place: the captured graphs address it through the words)
+    return loop_table_install(f, &f->lin_points, who, count, f->d, u_cd);
 }
 
 int pnmol_filter_linearization_pending(const pnmol_filter* f, int* next, int* count) {
-    if (!f) return -1;
-    if (next) *next = f->lin_plan ? f->lin_plan->plan.next : 0;
-    if (count) *count = f->lin_plan ? f->lin_plan->plan.count : 0;
-    return 0;
+    return f ? loop_table_pending(f->lin_points, next, count) : -1;
 }
 
 int pnmol_filter_linearize_at(pnmol_filter* f, const double* u_d) {

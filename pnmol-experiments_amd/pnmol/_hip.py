@@ -441,6 +441,16 @@ class Filter:
         self.ctx.check(self.lib.pnmol_filter_linearize(self.handle, state_in.handle, float(dt)), "pnmol_filter_linearize")
         self.error_model_dt = None
 
+    def _pending(self, name):
+        """(next, count) of the loop option whose query is the library's `name`: its cursor and its length ((0, 0): none set)."""
+        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(getattr(self.lib, name)(self.handle, ctypes.byref(nxt), ctypes.byref(n)), name)
+        return nxt.value, n.value
+
+    def _clear(self, name, *nulls):
+        """The set call `name` of the library with the arguments that clear what it sets."""
+        self.ctx.check(getattr(self.lib, name)(self.handle, *nulls), name)
+
     def set_linearization_points(self, points):
         """Linearisation points for the constant-step loop (`pnmol_filter_set_linearization_points`): `points` (count, d),
         derivative 0 in raw coordinates; the i-th step `steps` takes from now on linearises the term at row i in place of its own
@@ -454,15 +464,11 @@ class Filter:
 
     def clear_linearization_points(self):
         """Drop the table: the filter then takes the launches and gives the bits of one that never had a table."""
-        self.ctx.check(self.lib.pnmol_filter_set_linearization_points(self.handle, 0, None),
-                       "pnmol_filter_set_linearization_points")
+        self._clear("pnmol_filter_set_linearization_points", 0, None)
 
     def linearization_pending(self):
         """(next, count): the table's cursor -- the row the next step is linearised at -- and its number of rows ((0, 0): none)."""
-        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
-        self.ctx.check(self.lib.pnmol_filter_linearization_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
-                       "pnmol_filter_linearization_pending")
-        return nxt.value, n.value
+        return self._pending("pnmol_filter_linearization_pending")
 
     def linearize_at(self, u):
         """Enqueue the EK1 linearisation of the term at the point `u` (d,) (`pnmol_filter_linearize_at`; no synchronisation).  Then
@@ -481,14 +487,11 @@ class Filter:
 
     def clear_forcing(self):
         """Drop the table: the filter then takes the launches and gives the bits of one that never had a table."""
-        self.ctx.check(self.lib.pnmol_filter_set_forcing(self.handle, 0, None), "pnmol_filter_set_forcing")
+        self._clear("pnmol_filter_set_forcing", 0, None)
 
     def forcing_pending(self):
         """(next, count): the table's cursor -- the row the next step measures against -- and its number of rows ((0, 0): none)."""
-        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
-        self.ctx.check(self.lib.pnmol_filter_forcing_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
-                       "pnmol_filter_forcing_pending")
-        return nxt.value, n.value
+        return self._pending("pnmol_filter_forcing_pending")
 
     def force_at(self, rhs):
         """The right-hand side `rhs` (m,) every `step` measures against from now on (`pnmol_filter_force_at`; no
@@ -513,7 +516,7 @@ class Filter:
 
     def clear_operator_family(self):
         """Drop the family and its schedule: the filter then gives the bits of one that never had a family."""
-        self.ctx.check(self.lib.pnmol_filter_set_operator_family(self.handle, 0, None, None), "pnmol_filter_set_operator_family")
+        self._clear("pnmol_filter_set_operator_family", 0, None, None)
         self.operator_family = 0
         self._operator_schedule = False
         self.error_model_dt = None
@@ -531,15 +534,12 @@ class Filter:
 
     def clear_operator_schedule(self):
         """Drop the table: the operator stays what the last step made it."""
-        self.ctx.check(self.lib.pnmol_filter_set_operator_schedule(self.handle, 0, None), "pnmol_filter_set_operator_schedule")
+        self._clear("pnmol_filter_set_operator_schedule", 0, None)
         self._operator_schedule = False
 
     def operator_schedule_pending(self):
         """(next, count): the table's cursor -- the row the next step runs with -- and its number of rows ((0, 0): none)."""
-        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
-        self.ctx.check(self.lib.pnmol_filter_operator_schedule_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
-                       "pnmol_filter_operator_schedule_pending")
-        return nxt.value, n.value
+        return self._pending("pnmol_filter_operator_schedule_pending")
 
     def operator_at(self, coefficients):
         """The operator and its noise from the R coefficients (`pnmol_filter_operator_at`; enqueued at once, no synchronisation),
@@ -610,15 +610,11 @@ class Filter:
 
     def clear_observations(self):
         """Drop the sensor plan: the filter then takes the launches and gives the bits of one that never had a plan."""
-        self.ctx.check(self.lib.pnmol_filter_set_observations(self.handle, 0, None, 0, None, None, None),
-                       "pnmol_filter_set_observations")
+        self._clear("pnmol_filter_set_observations", 0, None, 0, None, None, None)
 
     def observations_pending(self):
         """(next, nobs): the plan's cursor -- the first entry that has not been applied -- and its length ((0, 0): no plan)."""
-        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
-        self.ctx.check(self.lib.pnmol_filter_observations_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
-                       "pnmol_filter_observations_pending")
-        return nxt.value, n.value
+        return self._pending("pnmol_filter_observations_pending")
 
     def observation_results(self, first=0, count=None):
         """ObserveOut of the applied plan entries [first, first + count) (default: up to the cursor)."""
@@ -650,15 +646,12 @@ class Filter:
 
     def clear_recorder(self):
         """Drop the recorder: the filter then takes the launches and gives the bits of one that never had a recorder."""
-        self.ctx.check(self.lib.pnmol_filter_set_recorder(self.handle, 0, None), "pnmol_filter_set_recorder")
+        self._clear("pnmol_filter_set_recorder", 0, None)
         self._recorder = None
 
     def recorder_pending(self):
         """(next, count): the recorder's cursor -- the slot the next step fills -- and its number of slots ((0, 0): none)."""
-        nxt, n = ctypes.c_int(0), ctypes.c_int(0)
-        self.ctx.check(self.lib.pnmol_filter_recorder_pending(self.handle, ctypes.byref(nxt), ctypes.byref(n)),
-                       "pnmol_filter_recorder_pending")
-        return nxt.value, n.value
+        return self._pending("pnmol_filter_recorder_pending")
 
     def recorder_means(self, first=0, count=None):
         """Means (count, n, d_state) of the filled slots [first, first + count) (default: up to the cursor), raw coordinates, in

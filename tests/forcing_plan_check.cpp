@@ -1,7 +1,7 @@
 // The host side of the loop's table of right-hand sides (csrc/pnmol_forcing_plan.hpp) on its own: built with
-// -fsanitize=address,undefined and run by tests/test_forcing_host.py.  Checks every refusal of the validation, the padded image of
-// a table, the step -> row mapping over split calls and a runt last step, the cursor after a failed call and a rehearsal, and the
-// refusal of a call; exits non-zero on the first violation.
+// -fsanitize=address,undefined and run by tests/test_forcing_host.py.  Checks every refusal of the validation and the padded image
+// of a table; exits non-zero on the first violation.  The table's cursor is that of every table of the loop:
+// tests/cursor_plan_check.cpp.
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -21,14 +21,6 @@ namespace {
 const char* g_case = "";
 
 bool contains(const std::string& s, const char* what) { return s.find(what) != std::string::npos; }
-
-ForcingPlan plan_of(int count, int m) {
-    const std::vector<double> rhs((size_t)count * m, 0.25);
-    REQUIRE(forcing_plan_validate(count, rhs.data(), m, false, false).empty());
-    ForcingPlan p;
-    forcing_plan_fill(&p, count, rhs.data());
-    return p;
-}
 
 void check_validation() {
     g_case = "validation";
@@ -62,13 +54,6 @@ void check_validation() {
     REQUIRE(forcing_plan_validate(0, nullptr, m, false, false).empty());
     REQUIRE(forcing_plan_validate(7, nullptr, m, false, false).empty());
     REQUIRE(contains(forcing_plan_validate(0, nullptr, m, false, true), "between"));
-    ForcingPlan p = plan_of(count, m);
-    REQUIRE(p.set() && p.count == 4 && p.next == 0 && p.left() == 4);
-    forcing_plan_fill(&p, 0, nullptr);
-    REQUIRE(!p.set() && p.count == 0 && p.next == 0);
-    REQUIRE(forcing_plan_begin(p, 1000).empty());  // no table: nothing to refuse
-    forcing_plan_collect(&p, 5, true);
-    REQUIRE(p.next == 0);
 }
 
 // the device image: row stride mp, padding zero (exact-size buffers on both sides)
@@ -83,58 +68,11 @@ void check_padding() {
         for (int j = 0; j < mp; ++j) REQUIRE(pad[(size_t)r * mp + j] == (j < m ? rhs[(size_t)r * m + j] : 0.0));
 }
 
-// 14 steps in calls of 13 + 1 (the runt last step is a call of its own: another dt), and in calls of 10 + 2 + 1 + 1
-void check_mapping() {
-    g_case = "mapping";
-    for (const std::vector<int>& calls : {std::vector<int>{13, 1}, std::vector<int>{10, 2, 1, 1}}) {
-        ForcingPlan p = plan_of(14, 2);
-        int taken = 0;
-        for (int k : calls) {
-            REQUIRE(forcing_plan_begin(p, k).empty());
-            for (int j = 0; j < k; ++j) REQUIRE(forcing_plan_row(p, j) == taken + j);
-            forcing_plan_collect(&p, k, true);
-            taken += k;
-            REQUIRE(p.next == taken && p.left() == 14 - taken);
-        }
-        REQUIRE(p.left() == 0);
-        REQUIRE(contains(forcing_plan_begin(p, 1), "1 step(s) asked for, 0 of 14 right-hand side(s) left"));
-        forcing_plan_collect(&p, 4, true);  // never past the end
-        REQUIRE(p.next == 14);
-        forcing_plan_collect(&p, -2, true);
-        REQUIRE(p.next == 14);
-    }
-}
-
-void check_call_refusals_and_rewinding() {
-    g_case = "call refusals, rewinding";
-    ForcingPlan p = plan_of(6, 5);
-    REQUIRE(forcing_plan_begin(p, 6).empty());
-    REQUIRE(contains(forcing_plan_begin(p, 7), "7 step(s) asked for, 6 of 6"));
-    forcing_plan_collect(&p, 4, true);
-    REQUIRE(forcing_plan_begin(p, 2).empty());
-    REQUIRE(contains(forcing_plan_begin(p, 3), "3 step(s) asked for, 2 of 6"));
-    REQUIRE(p.next == 4 && p.count == 6);  // a refused call leaves the plan as it was
-    // a call that failed consumes no row: the repeated call maps to the same rows
-    forcing_plan_collect(&p, 2, false);
-    REQUIRE(p.next == 4 && forcing_plan_row(p, 0) == 4 && forcing_plan_row(p, 1) == 5);
-    forcing_plan_collect(&p, 2, true);
-    REQUIRE(p.next == 6);
-    // a rehearsal: the cursor is read, the call collected, the cursor put back; values outside the table are clamped
-    forcing_plan_rewind(&p, 4);
-    REQUIRE(p.next == 4 && p.left() == 2);
-    forcing_plan_rewind(&p, -3);
-    REQUIRE(p.next == 0);
-    forcing_plan_rewind(&p, 99);
-    REQUIRE(p.next == 6);
-}
-
 }  // namespace
 
 int main() {
     check_validation();
     check_padding();
-    check_mapping();
-    check_call_refusals_and_rewinding();
     std::puts("forcing plan: ok");
     return 0;
 }

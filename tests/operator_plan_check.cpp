@@ -1,8 +1,8 @@
 // The host side of time-dependent operators (csrc/pnmol_operator_plan.hpp) on its own: built with -fsanitize=address,undefined and
 // run by tests/test_operator_host.py.  Checks every refusal of the three validations, the padded image of a table, the union image
 // of a family (columns ascending and packed, a slot for every entry of any operator and for the diagonal whatever the
-// coefficients, value planes, boundary rows and padding untouched, the width growing past the base), and the cursor over split
-// calls, a failed call and a rehearsal; exits non-zero on the first violation.
+// coefficients, value planes, boundary rows and padding untouched, the width growing past the base); exits non-zero on the first
+// violation.  The schedule's cursor is that of every table of the loop: tests/cursor_plan_check.cpp.
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -160,37 +160,12 @@ void check_image() {
     for (int i = 0; i < d; ++i) REQUIRE(g.img.col[(size_t)g.img.slot[i] * mp + i] == i);
 }
 
-void check_cursor() {
-    g_case = "cursor";
-    std::vector<double> a(14, 1.0);
-    OperatorPlan p;
-    operator_plan_fill(&p, 14, a.data());
-    int taken = 0;
-    for (int k : {10, 2, 1, 1}) {
-        REQUIRE(operator_plan_begin(p, k).empty());
-        for (int j = 0; j < k; ++j) REQUIRE(operator_plan_row(p, j) == taken + j);
-        operator_plan_collect(&p, k, true);
-        taken += k;
-        REQUIRE(p.next == taken);
-    }
-    REQUIRE(contains(operator_plan_begin(p, 1), "1 step(s) asked for, 0 of 14 row(s) of coefficients left"));
-    operator_plan_rewind(&p, 4);
-    REQUIRE(p.next == 4);
-    operator_plan_collect(&p, 3, false);  // a call that failed consumes none
-    REQUIRE(p.next == 4 && operator_plan_row(p, 0) == 4);
-    operator_plan_rewind(&p, 99);
-    REQUIRE(p.next == 14);
-    operator_plan_fill(&p, 0, nullptr);
-    REQUIRE(!p.set() && operator_plan_begin(p, 1000).empty());
-}
-
 }  // namespace
 
 int main() {
     check_validation();
     check_padding();
     check_image();
-    check_cursor();
     std::puts("operator plan: ok");
     return 0;
 }

@@ -225,6 +225,31 @@ def test_two_calls_equal_one_call_and_the_rehearsal_rewinds(hip_ctx):
     assert np.array_equal(a.mean(), b.mean()) and np.array_equal(a.cov(), b.cov()) and a.t == b.t
 
 
+def test_second_table_on_the_same_filter_replays_the_graphs(hip_ctx):
+    """A table that fits the one before it is overwritten in place and the captured graphs of the first run serve the second: its
+    result equals that of a fresh filter bit for bit."""
+    shape = fr.SHAPES[0]
+    pde, solver, flt, s0 = _bound(shape, "both")
+    ts, _ = solver._constant_schedule(pde, None)
+    table = pde.forcing.table(ts, pde)
+    second = np.ascontiguousarray(-0.7 * table[::-1])
+    flt.prepare_error_model(fr.DT)
+    flt.set_forcing(table)
+    first = flt.steps(s0.clone(), fr.STEPS, fr.DT)
+    flt.set_forcing(second)
+    assert flt.forcing_pending() == (0, fr.STEPS)
+    w = s0.clone()
+    again = flt.steps(w, fr.STEPS, fr.DT)
+    assert np.abs(again[0] - first[0]).max() > 1e-3 * np.abs(first[0]).max()
+    _, _, oflt, q0 = _bound(shape, "both")
+    oflt.prepare_error_model(fr.DT)
+    oflt.set_forcing(second)
+    fresh = oflt.steps(q0, fr.STEPS, fr.DT)
+    assert np.array_equal(again[0], fresh[0]) and np.array_equal(again[1], fresh[1])
+    assert [o.diffusion_squared_local for o in again[2]] == [o.diffusion_squared_local for o in fresh[2]]
+    assert np.array_equal(w.mean(), q0.mean()) and np.array_equal(w.cov(), q0.cov())
+
+
 def test_zero_table_and_cleared_table_give_the_unforced_bits(hip_ctx):
     """On the filter of the unforced problem: an all-zero table gives the unforced `solve()` result bit for bit (0 - 0 = +0 is the
     shift a linear filter has anyway), and a filter whose table was cleared gives the bits of a filter that never had one."""

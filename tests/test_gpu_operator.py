@@ -353,6 +353,61 @@ def test_linearisation_points_and_the_iterated_smoother_compose_with_the_operato
     assert_mean_std_parity(got.means, got.stds, it.means, it.stds)
 
 
+def _bound_with_three_tables():
+    """(filter, initial device state, K, (schedule, right-hand sides, points)): the forced logistic problem on kappa(t), the device
+    bound, and the K rows of each per-step table of its loop -- not yet set."""
+    pde, solver, _, _ = orf.logistic_pair(forcing=Forcing(source=_source), source=_source)
+    s0 = solver.initialize(pde).y.device_state
+    ts, _ = solver._constant_schedule(pde, None)
+    _, om, _ = orf.logistic_reference()
+    tables = (pde.time_dependent_operator.table(ts), pde.forcing.table(ts, pde), np.ascontiguousarray(1.01 * om[1:]))
+    assert all(len(rows) == orf.LOGISTIC[3] for rows in tables)
+    return solver._device_filter, s0, orf.LOGISTIC[3], tables
+
+
+def _set_three(flt, tables):
+    flt.set_operator_schedule(tables[0])
+    flt.set_forcing(tables[1])
+    flt.set_linearization_points(tables[2])
+
+
+def _cursors(flt):
+    return flt.linearization_pending(), flt.forcing_pending(), flt.operator_schedule_pending()
+
+
+def test_three_tables_in_one_loop(hip_ctx):
+    """Operator schedule, right-hand sides and linearisation points together: the rehearsal rewinds all three cursors, and one call
+    of K steps equals calls of 5 and K - 5 on a second filter bit for bit."""
+    flt, s0, K, tables = _bound_with_three_tables()
+    _set_three(flt, tables)
+    assert _cursors(flt) == ((0, K),) * 3
+    a = s0.clone()
+    flt.prepare_steps(a, K, DT)
+    assert _cursors(flt) == ((0, K),) * 3 and np.array_equal(a.mean(), s0.mean()) and np.array_equal(a.cov(), s0.cov())
+    m, s, i = flt.steps(a, K, DT)
+    assert _cursors(flt) == ((K, K),) * 3
+    oflt, b, _, _ = _bound_with_three_tables()
+    _set_three(oflt, tables)
+    m1, s1, i1 = oflt.steps(b, 5, DT)
+    assert _cursors(oflt) == ((5, K),) * 3
+    m2, s2, i2 = oflt.steps(b, K - 5, DT)
+    assert _cursors(oflt) == ((K, K),) * 3
+    assert np.array_equal(np.vstack((m1, m2)), m) and np.array_equal(np.vstack((s1, s2)), s)
+    assert _sig(list(i1) + list(i2)) == _sig(i)
+    assert np.array_equal(a.mean(), b.mean()) and np.array_equal(a.cov(), b.cov()) and a.t == b.t
+
+
+def test_refusal_with_three_tables_names_the_short_one(hip_ctx):
+    flt, s0, K, tables = _bound_with_three_tables()
+    _set_three(flt, (tables[0], tables[1][:K - 1], tables[2]))
+    w = s0.clone()
+    with pytest.raises(_hip.PnmolHipError,
+                       match=rf"forcing: {K} step\(s\) asked for, {K - 1} of {K - 1} right-hand side\(s\) left"):
+        flt.steps(w, K, DT)
+    assert _cursors(flt) == ((0, K), (0, K - 1), (0, K))
+    assert w.t == s0.t and np.array_equal(w.mean(), s0.mean()) and np.array_equal(w.cov(), s0.cov())
+
+
 # ------------------------------------------------------------------------------------------------------------------ 8. backward pass
 @pytest.mark.parametrize("family, shape", [("A", orf.SHAPES[0]), ("A", orf.SHAPES[1]), ("B", orf.SHAPES[1])])
 def test_backward_pass_on_a_recorded_solution(hip_ctx, family, shape):

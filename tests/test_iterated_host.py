@@ -1,6 +1,7 @@
 """CPU tests of the iterated EK1 smoother (`pnmol_filter_set_linearization_points`, `pnmol_filter_linearize_at`, `solve_iterated`;
 DESIGN.md section 22): the host logic of the table of linearisation points (csrc/pnmol_linearize_plan.hpp, nothing of HIP in it)
-under AddressSanitizer + UBSan -- tests/linearize_plan_check.cpp is a stand-alone program that includes nothing but that header --,
+under AddressSanitizer + UBSan -- tests/linearize_plan_check.cpp is a stand-alone program that includes nothing but that header, and
+tests/cursor_plan_check.cpp one for the cursor that every table of the loop shares (csrc/pnmol_cursor_plan.hpp) --,
 the C ABI's new names, the refusals of `solve_iterated` and of `linearize_at` in front of any device work, and the conditions that
 the cases of tests/test_gpu_iterated.py must meet on the NumPy reference alone (tests/iterated_reference.py).  No GPU."""
 
@@ -22,15 +23,25 @@ RESULT = pnmol.white.IteratedSolution      # (the feature's own name at import: 
 NAMES = ("pnmol_filter_set_linearization_points", "pnmol_filter_linearization_pending", "pnmol_filter_linearize_at")
 
 
-@pytest.mark.skipif(not CLANG.exists(), reason="the ROCm clang++ is not available")
-def test_linearize_plan_host_logic_under_asan_ubsan(tmp_path):
-    exe = tmp_path / "linearize_plan_check"
+def _check_program(tmp_path, name, says):
+    exe = tmp_path / name
     subprocess.run([str(CLANG), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{ROOT / 'pnmol-experiments_amd' / 'csrc'}", str(ROOT / "tests" / "linearize_plan_check.cpp"), "-o", str(exe)],
+                    f"-I{ROOT / 'pnmol-experiments_amd' / 'csrc'}", str(ROOT / "tests" / f"{name}.cpp"), "-o", str(exe)],
                    check=True)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert run.stdout.strip() == "linearize plan: ok" and "runtime error" not in run.stderr
+    assert run.stdout.strip() == says and "runtime error" not in run.stderr
+
+
+@pytest.mark.skipif(not CLANG.exists(), reason="the ROCm clang++ is not available")
+def test_linearize_plan_host_logic_under_asan_ubsan(tmp_path):
+    _check_program(tmp_path, "linearize_plan_check", "linearize plan: ok")
+
+
+@pytest.mark.skipif(not CLANG.exists(), reason="the ROCm clang++ is not available")
+def test_cursor_plan_host_logic_under_asan_ubsan(tmp_path):
+    """The cursor and the set-call rule that the table of points shares with the loop's other tables (csrc/pnmol_cursor_plan.hpp)."""
+    _check_program(tmp_path, "cursor_plan_check", "cursor plan: ok")
 
 
 def test_iterated_symbols_are_declared_and_exported():
